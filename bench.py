@@ -30,6 +30,15 @@ thread and at all CPUs this process may use.
 --device cpu runs the same harness with the CPU emulation of the kernel
 (rhp_emu_parse_batch) instead of the GPU: a test of the launcher, sharding and
 reduction on machines without a GPU, never a measurement.
+
+A plain run (`--gpus N --steps K --warmup W`) does what `value` needs and no
+more: it sets the batches up, warms up, times the K steps and prints the line.
+--full adds everything else the line can carry: the single-stream pass
+(roofline, single_stream), ok_fraction, the parity check against the
+reference's digests, extra_configs, the e2e leg and cpu_baseline.
+--dump-outputs DIR writes the records of the last timed launch as .npy arrays
+(dump_outputs): the inputs are generated from fixed seeds, so two builds run
+with the same arguments compare array for array.
 """
 from __future__ import annotations
 
@@ -244,13 +253,15 @@ class GpuRunner:
     """A config's shard resident in HBM (rotated copies), launched on torch's
     current stream and timed with HIP events on that stream."""
 
-    def __init__(self, cfg, lo, hi, copies, layout, streams=1):
+    def __init__(self, cfg, lo, hi, copies, layout, streams=1, hash_input=True):
         import hashlib
         import torch
         self.torch = torch
         self.mode = cfg["mode"]
         buf, off = rhp.generate(cfg["gen"], hi - lo, cfg["seed"], lo=lo)
-        self.input_sha256 = hashlib.sha256(buf.tobytes()).hexdigest()
+        self.off = off
+        # the parity check (--full) ties the reference digest to these input bytes
+        self.input_sha256 = hashlib.sha256(buf.tobytes()).hexdigest() if hash_input else None
         # a config whose launches rewrite the bytes (chunked bodies, http.c:155) restores a copy from
         # this pristine one before it is launched again: >= 3 copies, restored two launches ahead
         self.rewrites = bool(cfg.get("rewrites"))
@@ -391,8 +402,12 @@ class EmuRunner:
     def __init__(self, cfg, lo, hi, copies, layout):
         self.buf, self.off = rhp.generate(cfg["gen"], hi - lo, cfg["seed"], lo=lo)
         self.cfg = cfg
+        self.mode = cfg["mode"]
         self.layout = layout
         self.res = None
+
+    def last_result(self):
+        return self.res
 
     def poison(self):
         self.res = None
@@ -441,7 +456,55 @@ def golden_spec(key, lo, n):
     return None
 
 
-def run_config(key, args, rank, world, per_gpu, steps, warmup, dist, streams=1):
+DUMP_SEED = 0x5EED0D0D            # --dump-outputs: the sampled requests are the same in every run
+DUMP_SAMPLE_BYTES = 40 << 20      # the sampled records' share of the 64 MB a dump may take
+DUMP_ALL_RETS = 1 << 21           # `ret` of every request is written for shards up to this many requests
+
+
+def dump_outputs(outdir, res, off, mode):
+    """--dump-outputs DIR: what the last timed launch computed, as DIR/<name>.npy
+    (float32; float64 where a value may pass 2^24), so two builds compare array
+    for array.  The records are the ones a caller of parse_batch receives
+    (Result: reqs, hdrs[n, max_headers], http), canonical (rhp.canonical: the
+    fields the reference leaves unspecified for a request that did not parse
+    zeroed).  A shard too large for the budget is written as a fixed, seeded
+    sample of its requests (sample_index); `ret` of every request besides.
+      ret           [n]        phr_parse_request's return value per request
+      sample_index  [S]        the sampled requests (ascending)
+      reqs          [S, 8]     REQ_DTYPE's fields in order
+      hdrs          [S, max_headers, 4]  name_off, name_len, value_off, value_len
+      http          [S, 4]     result, body_kind, consumed, body_len (http mode)
+      bytes_crc32   [S]        crc32 of the request's bytes as the launch left
+                               them (http mode: chunked bodies de-framed in place)
+    Returns {name: shape}."""
+    import zlib
+    os.makedirs(outdir, exist_ok=True)
+    reqs, hdrs, http = rhp.canonical(res, mode)
+    n, maxh = len(reqs), hdrs.shape[1]
+    per_req = 8 + 4 * len(reqs.dtype.names) + 16 * maxh + (40 if mode == rhp.MODE_HTTP else 0)
+    sample = min(n, DUMP_SAMPLE_BYTES // per_req)
+    idx = np.arange(n) if sample == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, sample, replace=False))
+    out = {"sample_index": idx.astype(np.float64),
+           "reqs": np.stack([reqs[f][idx].astype(np.float32) for f in reqs.dtype.names], axis=1),
+           "hdrs": np.stack([hdrs[f][idx].astype(np.float32) for f in hdrs.dtype.names], axis=2)}
+    if n <= DUMP_ALL_RETS:
+        out["ret"] = reqs["ret"].astype(np.float32)
+    if mode == rhp.MODE_HTTP:
+        out["http"] = np.stack([http[f][idx].astype(np.float64) for f in http.dtype.names], axis=1)
+        if res.bytes_out is not None:
+            raw = memoryview(np.ascontiguousarray(res.bytes_out))
+            out["bytes_crc32"] = np.array([zlib.crc32(raw[int(off[i]):int(off[i + 1])]) for i in idx], dtype=np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
+def run_config(key, args, rank, world, per_gpu, steps, warmup, dist, streams=1, full=True, dump=None):
+    """One config set up, warmed up and timed.  A plain run (full=False) times
+    only what `value` is made of: the K steps alternating over `streams` HIP
+    streams (or the K single-stream steps where streams is 1).  full=True adds
+    the single-stream pass (per-launch kernel time: roofline, single_stream),
+    ok_fraction and the parity check against the reference's digest."""
     cfg = CONFIGS[key]
     n_total = per_gpu * world
     lo, hi = shard_range(n_total, rank, world)
@@ -451,23 +514,25 @@ def run_config(key, args, rank, world, per_gpu, steps, warmup, dist, streams=1):
     lay_name = over.get(key, cfg["layout"]) if args.layout == "auto" else args.layout
     layout = LAYOUTS[lay_name]
     streams = streams if args.device == "gpu" and not cfg.get("rewrites") else 1
-    runner = (GpuRunner(cfg, lo, hi, max(args.copies, streams), layout, streams=streams) if args.device == "gpu"
-              else EmuRunner(cfg, lo, hi, args.copies, layout))
-    for k in range(warmup):
-        runner.step(k)
-    runner.sync()
-    ok_frac = runner.ok_fraction()
-    runner.poison()   # the records the parity check hashes are the timed launches' own
-    if dist is not None:
-        dist.barrier()
-    runner.sync()
-    wall, kern_ms = runner.timed(steps)
-    if dist is not None:
-        dist.barrier()
-    single = None
+    runner = (GpuRunner(cfg, lo, hi, max(args.copies, streams), layout, streams=streams, hash_input=full)
+              if args.device == "gpu" else EmuRunner(cfg, lo, hi, args.copies, layout))
+    wall, kern_ms, ok_frac, single = None, None, None, None
+    if full or streams == 1:
+        for k in range(warmup):
+            runner.step(k)
+        runner.sync()
+        if full:
+            ok_frac = runner.ok_fraction()
+        runner.poison()   # the records the parity check hashes are the timed launches' own
+        if dist is not None:
+            dist.barrier()
+        runner.sync()
+        wall, kern_ms = runner.timed(steps)
+        if dist is not None:
+            dist.barrier()
     if streams > 1:
         # the same K steps with the batches alternating over `streams` HIP streams: the
-        # value's timed region (the single-stream one above gives the kernel time)
+        # value's timed region (the single-stream one above, --full only, gives the kernel time)
         single = wall
         runner.timed_pipelined(warmup)
         runner.poison()
@@ -477,35 +542,39 @@ def run_config(key, args, rank, world, per_gpu, steps, warmup, dist, streams=1):
         wall = runner.timed_pipelined(steps)
         if dist is not None:
             dist.barrier()
-    # outside the timed region: the last timed launch's records against the reference's digest
-    spec = golden_spec(key, lo, hi - lo)
-    parity = runner.parity(spec)
-    parity_entry = {"result": parity, "digest": spec["name"] if spec else None}
-    if parity.startswith("MISMATCH"):
-        print(f"bench.py: PARITY {key} rank {rank}: {parity}", file=sys.stderr)
+    dumped = dump_outputs(dump, runner.last_result(), runner.off, cfg["mode"]) if dump else None
+    parity_entry = None
+    if full:
+        # outside the timed region: the last timed launch's records against the reference's digest
+        spec = golden_spec(key, lo, hi - lo)
+        parity = runner.parity(spec)
+        parity_entry = {"result": parity, "digest": spec["name"] if spec else None}
+        if parity.startswith("MISMATCH"):
+            print(f"bench.py: PARITY {key} rank {rank}: {parity}", file=sys.stderr)
     total_alg = float(alg_bytes)
     if dist is not None:
         import torch
-        t = torch.tensor([wall, kern_ms, single or 0.0], dtype=torch.float64)
+        t = torch.tensor([wall, kern_ms or 0.0, single or 0.0], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        wall, kern_ms = float(t[0]), float(t[1])
+        wall, kern_ms = float(t[0]), float(t[1]) if kern_ms is not None else None
         single = float(t[2]) if single is not None else None
         tb = torch.tensor([float(alg_bytes)], dtype=torch.float64)
         dist.all_reduce(tb)
         total_alg = float(tb[0])
-        # every rank's verdict reaches rank 0's line (0 match, 1 unpinned, 2 mismatch)
-        code = 2 if parity.startswith("MISMATCH") else 0 if parity == "match" else 1
-        codes = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
-        dist.all_gather(codes, torch.tensor([code], dtype=torch.int64))
-        parity_entry["ranks"] = ["match" if int(c) == 0 else "unpinned" if int(c) == 1 else "MISMATCH" for c in codes]
-        if any(int(c) == 2 for c in codes):
-            parity_entry["result"] = "MISMATCH on some rank"
-        elif any(int(c) == 1 for c in codes):
-            parity_entry["result"] = "match on the ranks with a reference digest" if any(int(c) == 0 for c in codes) \
-                else parity_entry["result"]
+        if full:
+            # every rank's verdict reaches rank 0's line (0 match, 1 unpinned, 2 mismatch)
+            code = 2 if parity.startswith("MISMATCH") else 0 if parity == "match" else 1
+            codes = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+            dist.all_gather(codes, torch.tensor([code], dtype=torch.int64))
+            parity_entry["ranks"] = ["match" if int(c) == 0 else "unpinned" if int(c) == 1 else "MISMATCH" for c in codes]
+            if any(int(c) == 2 for c in codes):
+                parity_entry["result"] = "MISMATCH on some rank"
+            elif any(int(c) == 1 for c in codes):
+                parity_entry["result"] = "match on the ranks with a reference digest" if any(int(c) == 0 for c in codes) \
+                    else parity_entry["result"]
     return dict(cfg=cfg, lo=lo, hi=hi, n_total=n_total, alg_bytes=alg_bytes, total_alg=total_alg, wall=wall,
                 kern_ms=kern_ms, ok_frac=ok_frac, steps=steps, warmup=warmup, parity=parity_entry, layout=lay_name,
-                streams=streams, single_wall=single)
+                streams=streams, single_wall=single, dumped=dumped)
 
 
 def roofline(r, key):
@@ -522,9 +591,17 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the single-stream pass (kernel time, roofline, single_stream), "
+                         "ok_fraction, the parity check against the reference's digests, the extra configs, the "
+                         "host-memory end-to-end leg and the CPU baseline (--extra, --no-e2e and --no-cpu trim it).  "
+                         "Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last timed launch (rank 0's shard) as "
+                         "DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--config", default="get256", choices=sorted(CONFIGS))
     ap.add_argument("--extra", default="auto", choices=["auto", "none"],
-                    help="auto: at N=1 also time configs 3 and 5 and the chunked config (extra_configs)")
+                    help="with --full; auto: at N=1 also time configs 3 and 5 and the chunked config (extra_configs)")
     ap.add_argument("--extra-steps", type=int, default=20)
     ap.add_argument("--extras", default=",".join(EXTRA_KEYS), help="comma list of the extra configs to time")
     ap.add_argument("--copies", type=int, default=4)
@@ -534,8 +611,8 @@ def main(argv=None):
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams the timed batches of the main config alternate over (`value`): two batches "
                          "in flight, as the reactor's two slots, so one batch's tail overlaps the next one's start; "
-                         "1 = one stream.  The single-stream rate and the per-launch kernel time (roofline) are "
-                         "measured too, on one stream")
+                         "1 = one stream.  With --full the single-stream rate and the per-launch kernel time "
+                         "(roofline) are measured too, on one stream")
     ap.add_argument("--impl", type=int, default=rhp.IMPL_DFA)
     ap.add_argument("--device", default="gpu", choices=["gpu", "cpu"])
     ap.add_argument("--layout", default="auto", choices=["auto"] + sorted(LAYOUTS),
@@ -565,9 +642,10 @@ def main(argv=None):
         rhp.lib().rhp_set_impl(args.impl)
     per_gpu = args.per_gpu or CONFIGS[args.config]["per_gpu"]
 
-    r = run_config(args.config, args, rank, world, per_gpu, args.steps, args.warmup, dist, streams=max(1, args.streams))
+    r = run_config(args.config, args, rank, world, per_gpu, args.steps, args.warmup, dist, streams=max(1, args.streams),
+                   full=args.full, dump=args.dump_outputs if rank == 0 else None)
     extra = {}
-    if world == 1 and args.extra == "auto" and args.config == "get256":
+    if args.full and world == 1 and args.extra == "auto" and args.config == "get256":
         for key in [k for k in args.extras.split(",") if k in EXTRA_KEYS]:
             e = run_config(key, args, rank, world, args.per_gpu or CONFIGS[key]["per_gpu"], args.extra_steps,
                            3, None)
@@ -593,16 +671,21 @@ def main(argv=None):
             "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
             "config": {"workload": cfg["name"], "requests_per_gpu": r["hi"] - r["lo"], "global_requests": r["n_total"],
                        "algorithmic_bytes_per_gpu": int(r["alg_bytes"]), "resident_copies": args.copies,
-                       "max_headers": cfg["maxh"], "parallelism": f"shard{world}", "ok_fraction": r["ok_frac"],
+                       "max_headers": cfg["maxh"], "parallelism": f"shard{world}",
                        "kernel": kernel, "device": args.device, "record_layout": f"{r['layout']}-major"},
-            "roofline": roofline(r, args.config),
         }
-        # parity of every timed workload: the records of its last timed launch
-        # hashed against the reference's digest (GOLDEN_DIGESTS)
-        line["parity"] = {("config4" if world > 1 else "config2") if args.config == "get256" else args.config:
-                          r["parity"]["result"]}
-        line["parity"].update({k: v["parity"]["result"] for k, v in extra.items()})
-        line["parity_detail"] = {args.config: r["parity"], **{k: v["parity"] for k, v in extra.items()}}
+        if r["kern_ms"] is not None:   # the per-launch kernel time: --full, or a run on one stream
+            line["roofline"] = roofline(r, args.config)
+        if args.full:
+            line["config"]["ok_fraction"] = r["ok_frac"]
+            # parity of every timed workload: the records of its last timed launch
+            # hashed against the reference's digest (GOLDEN_DIGESTS)
+            line["parity"] = {("config4" if world > 1 else "config2") if args.config == "get256" else args.config:
+                              r["parity"]["result"]}
+            line["parity"].update({k: v["parity"]["result"] for k, v in extra.items()})
+            line["parity_detail"] = {args.config: r["parity"], **{k: v["parity"] for k, v in extra.items()}}
+        if r["dumped"] is not None:
+            line["dumped_outputs"] = r["dumped"]
         line["library_sha256"] = rhp.library_sha256() if args.device == "gpu" else None
         line["batches_in_flight"] = r["streams"]
         if r.get("single_wall") is not None:
@@ -611,7 +694,7 @@ def main(argv=None):
                                      "note": "the same K steps on one HIP stream (one batch at a time)"}
         if extra:
             line["extra_configs"] = extra
-        if world == 1 and args.device == "gpu" and not args.no_e2e:
+        if args.full and world == 1 and args.device == "gpu" and not args.no_e2e:
             # north_star: the path starts and ends in host memory; the rate with
             # pinned H2D -> kernel -> records written into mapped host memory,
             # chunked over 3 streams (never `value`, which is device-resident).
@@ -630,10 +713,11 @@ def main(argv=None):
             except Exception as exc:
                 line["e2e"] = {"error": repr(exc)[-2000:]}
                 print(f"bench.py: e2e leg failed: {exc!r}", file=sys.stderr)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline([args.config] + [k for k in EXTRA_KEYS if k in extra])
         print(json.dumps(line), flush=True)
-    bad = "MISMATCH" in r["parity"]["result"] or any("MISMATCH" in v["parity"]["result"] for v in extra.values())
+    bad = args.full and ("MISMATCH" in r["parity"]["result"]
+                         or any("MISMATCH" in v["parity"]["result"] for v in extra.values()))
     if dist is not None:
         dist.destroy_process_group()
     if bad and not os.environ.get("RHP_BENCH_DIAG"):   # RHP_BENCH_DIAG: diagnostic builds that write wrong records on purpose

@@ -7,6 +7,7 @@ import socket
 import tempfile
 
 import numpy as np
+import pytest
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
@@ -76,7 +77,7 @@ def test_bench_launches_its_own_ranks():
     """`bench.py --gpus 2` without a launcher starts 2 rank processes itself
     (gloo control plane, contiguous shards, max-over-ranks time, summed bytes);
     --device cpu runs the kernel's CPU emulation in place of the GPU."""
-    rc, line, err = _bench(["--gpus", "2", "--device", "cpu", "--steps", "2", "--warmup", "1", "--no-cpu",
+    rc, line, err = _bench(["--gpus", "2", "--device", "cpu", "--steps", "2", "--warmup", "1", "--full", "--no-cpu",
                             "--per-gpu", "32768"])
     assert rc == 0, err
     assert line["n_gpus"] == 2 and line["config"]["parallelism"] == "shard2"
@@ -88,3 +89,71 @@ def test_bench_rejects_world_size_mismatch():
     rc, line, _ = _bench(["--gpus", "4", "--device", "cpu", "--steps", "1", "--no-cpu", "--per-gpu", "1024"],
                          env={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert rc == 2 and line is None
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain run carries the headline keys and none of the --full legs;
+    --dump-outputs writes the last timed step's records as float arrays, the
+    same from run to run and equal to a direct parse of the same requests."""
+    n = 3000
+    dumps = []
+    for d in ("a", "b"):
+        rc, line, err = _bench(["--gpus", "1", "--device", "cpu", "--config", "zipf", "--steps", "2", "--warmup", "1",
+                                "--per-gpu", str(n), "--dump-outputs", str(tmp_path / d)])
+        assert rc == 0, err
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+        for key in ("parity", "extra_configs", "e2e", "cpu_baseline", "single_stream"):
+            assert key not in line
+        arrays = {f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))}
+        assert sorted(arrays) == sorted(line["dumped_outputs"]) == ["hdrs", "reqs", "ret", "sample_index"]
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        dumps.append(arrays)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    cfg = bench.CONFIGS["zipf"]
+    buf, off = rhp.generate(cfg["gen"], n, cfg["seed"])
+    res, _ = rhp.emulate(buf, off, cfg["maxh"], cfg["mode"])
+    reqs, hdrs, _ = rhp.canonical(res, cfg["mode"])
+    got = dumps[0]
+    assert np.array_equal(got["sample_index"], np.arange(n))
+    assert np.array_equal(got["ret"], reqs["ret"].astype(np.float32))
+    assert got["reqs"].shape == (n, len(reqs.dtype.names)) and got["hdrs"].shape == (n, cfg["maxh"], 4)
+    for j, f in enumerate(reqs.dtype.names):
+        assert np.array_equal(got["reqs"][:, j], reqs[f].astype(np.float32)), f
+    for j, f in enumerate(hdrs.dtype.names):
+        assert np.array_equal(got["hdrs"][:, :, j], hdrs[f].astype(np.float32)), f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key,n", [("get256", 150001), ("chunked", 20001)])
+def test_bench_gpu_dump_matches_host_parser(key, n, tmp_path):
+    """--dump-outputs on the GPU: the records of the last timed launch (two
+    streams for config 2, one for the chunked config, whose launches rewrite
+    their bytes) equal the host's exact parser on the same requests; 150001
+    requests are more than a dump holds, so config 2's is the seeded sample."""
+    import zlib
+    cfg = bench.CONFIGS[key]
+    rc, line, err = _bench(["--gpus", "1", "--config", key, "--steps", "3", "--warmup", "1", "--per-gpu", str(n),
+                            "--dump-outputs", str(tmp_path)])
+    assert rc == 0, err
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and "parity" not in line and "cpu_baseline" not in line
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(got) == sorted(line["dumped_outputs"])
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    buf, off = rhp.generate(cfg["gen"], n, cfg["seed"])
+    res = rhp.parse_cpu_exact(buf, off, cfg["maxh"], cfg["mode"])
+    reqs, hdrs, http = rhp.canonical(res, cfg["mode"])
+    idx = got["sample_index"].astype(np.int64)
+    assert (len(idx) < n) == (key == "get256") and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    assert np.array_equal(got["ret"], reqs["ret"].astype(np.float32))
+    for j, f in enumerate(reqs.dtype.names):
+        assert np.array_equal(got["reqs"][:, j], reqs[f][idx].astype(np.float32)), f
+    for j, f in enumerate(hdrs.dtype.names):
+        assert np.array_equal(got["hdrs"][:, :, j], hdrs[f][idx].astype(np.float32)), f
+    if cfg["mode"] == rhp.MODE_HTTP:
+        for j, f in enumerate(http.dtype.names):
+            assert np.array_equal(got["http"][:, j], http[f][idx].astype(np.float64)), f
+        want = [zlib.crc32(res.bytes_out[int(off[i]):int(off[i + 1])].tobytes()) for i in idx]
+        assert np.array_equal(got["bytes_crc32"], np.array(want, dtype=np.float64))
+    else:
+        assert "http" not in got and "bytes_crc32" not in got
