@@ -327,7 +327,14 @@ typedef struct rhp_resp_field {
 #define RHP_DATE_LEN 29u
 
 typedef struct rhp_resp_batch {
-  const uint8_t          *arena;    /* device */
+  const uint8_t          *arena;    /* device, any alignment.  The writer reads a span as the whole
+                                       aligned dwords that hold it: up to 3 bytes before a span's
+                                       first byte and up to 3 bytes beyond its last.  So the
+                                       arena's memory must be readable from the 4-byte boundary at
+                                       or below its first byte up to the next 4-byte boundary
+                                       after its last byte (an arena inside a device allocation
+                                       whose start and size are multiples of 4 is); an empty span
+                                       is not read at all, wherever its off points */
   const rhp_resp_t       *resps;    /* device [n] */
   const rhp_resp_field_t *fields;   /* device, may be NULL when no response has fields */
   uint32_t                n;

@@ -651,11 +651,63 @@ RESP_FIELD_NAMES = (b"Cookie", b"Set-Cookie", b"X-Request-Id", b"Cache-Control")
 DEFAULT_DATE = b"Wed, 16 Aug 2023 10:29:23 GMT"
 
 
+EDGE_SPAN_LENS = (0, 1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 143, 144, 145, 255, 256, 257,
+                  1023, 1024, 1025)
+EDGE_BODY_LENS = (0, 9, 10, 99, 100, 999, 1000, 9999, 10000)
+EDGE_FIELD_COUNTS = (0, 0, 1, 2, 7)
+EDGE_COOP_BODY = 17000   # larger than the writer's 16 KiB stage
+
+
+def _edge_responses(n: int, seed: int, coop: bool):
+    """make_responses kinds "edge" and "edge-coop" (vectorised: one draw per column)"""
+    rng = np.random.default_rng(seed)
+    arena = rng.integers(0x20, 0x7F, size=(1 << 15) + 3, dtype=np.uint8)   # (a length that is no multiple of 4)
+    lens = np.array(EDGE_SPAN_LENS, dtype=np.int64)
+
+    def spans(ln):
+        """a random start for every length; a quarter of the empty spans at the arena's end"""
+        off = rng.integers(0, len(arena) - ln + 1)
+        at_end = (ln == 0) & (rng.random(len(ln)) < 0.25)
+        return np.where(at_end, len(arena), off)
+
+    def pick(count):
+        return lens[rng.integers(0, len(lens), size=count)]
+
+    st, ty = pick(n), pick(n)
+    body = np.where(rng.random(n) < 0.5, pick(n),
+                    np.array(EDGE_BODY_LENS, dtype=np.int64)[rng.integers(0, len(EDGE_BODY_LENS), size=n)])
+    if coop:
+        body[::64] = EDGE_COOP_BODY
+    nf = np.array(EDGE_FIELD_COUNTS, dtype=np.int64)[rng.integers(0, len(EDGE_FIELD_COUNTS), size=n)]
+    m = int(nf.sum())
+    name, value = pick(m), pick(m)
+    resps = np.zeros((n, 8), dtype=np.uint32)
+    for col, ln in ((0, st), (2, ty), (4, body)):
+        resps[:, col], resps[:, col + 1] = spans(ln), ln
+    resps[:, 6], resps[:, 7] = np.cumsum(nf) - nf, nf
+    fields = np.zeros((m, 4), dtype=np.uint32)
+    for col, ln in ((0, name), (2, value)):
+        fields[:, col], fields[:, col + 1] = spans(ln), ln
+    return arena, resps, fields
+
+
 def make_responses(n: int, seed: int, kind: str = "mixed"):
     """Synthetic response batch (arena, resps, fields).  kind "plaintext": every
     response is the TechEmpower plaintext reply (200 OK, text/plain,
     "Hello, World!"); "mixed": seeded statuses/types, 0-3 extra fields, body
-    lengths 0-2000 B with 1 % up to 100 kB (all digit counts of Content-Length)."""
+    lengths 0-2000 B with 1 % up to 100 kB (all digit counts of Content-Length).
+    "edge": every status, type, field name and field value, and half of the
+    bodies, has a length from EDGE_SPAN_LENS (around every power of two the
+    writer's copy loops step by, and the 128 B switch of its cooperative copy),
+    the other bodies one from EDGE_BODY_LENS (Content-Length digit counts);
+    every span starts at a random arena byte (all four source alignments), some
+    empty spans at the arena's end; EDGE_FIELD_COUNTS extra fields.
+    "edge-coop": "edge" with an EDGE_COOP_BODY-byte body in every 64th response,
+    so that every group of 64 is larger than the writer's stage."""
+    if kind in ("edge", "edge-coop"):
+        return _edge_responses(n, seed, kind == "edge-coop")
+    if kind not in ("plaintext", "mixed"):
+        raise ValueError(f"unknown response kind {kind!r}")
     rng = np.random.default_rng(seed)
     parts, pos = [], 0
 
@@ -692,16 +744,31 @@ def make_responses(n: int, seed: int, kind: str = "mixed"):
 
 
 class DeviceResponses:
-    """A response batch resident in HBM and its output (torch tensors as plumbing)."""
+    """A response batch resident in HBM and its output (torch tensors as plumbing).
+
+    out_shift, arena_shift (bytes, tests): the `out` and `arena` pointers handed
+    to the library are an allocation's base plus the shift, so every alignment
+    of either can be run.  guard (bytes, tests): that many bytes of 0xA5 lie
+    directly before and after the out_size bytes of `out`, and result() returns
+    them too.  out_size 0: `out` is NULL (sizes only, rhp.h)."""
+
+    GUARD_BYTE = 0xA5
 
     def __init__(self, arena: np.ndarray, resps: np.ndarray, fields: np.ndarray, date: bytes = DEFAULT_DATE,
-                 out_size: int | None = None, device: str = "cuda"):
+                 out_size: int | None = None, device: str = "cuda", out_shift: int = 0, arena_shift: int = 0,
+                 guard: int = 0):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the rhp product path runs on MI355X only")
         self.n = len(resps)
         self.date = bytes(date)
-        self.arena = torch.from_numpy(np.ascontiguousarray(arena, dtype=np.uint8)).to(device)
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        if arena_shift or len(arena) & 3:   # (the arena's bytes moved up;) readable to the next 4-byte boundary (rhp.h)
+            moved = np.full((arena_shift + len(arena) + 3) & ~3, 0xEE, dtype=np.uint8)
+            moved[arena_shift: arena_shift + len(arena)] = arena
+            arena = moved
+        self.arena = torch.from_numpy(arena).to(device)
+        self.arena_shift = arena_shift
         self.resps = torch.from_numpy(np.ascontiguousarray(resps, dtype=np.uint32).view(np.int32)).to(device)
         fl = np.ascontiguousarray(fields, dtype=np.uint32).reshape(-1, 4)
         self.fields = torch.from_numpy(fl.view(np.int32)).to(device) if len(fl) else None
@@ -715,15 +782,23 @@ class DeviceResponses:
                 extra = int(sum(int(per[a:a + c].sum()) for a, c in zip(r[:, 6], r[:, 7]) if c))
             digits = np.array([len(str(int(v))) for v in r[:, 5]], dtype=np.uint64)
             out_size = int((95 + r[:, 1] + r[:, 3] + r[:, 5] + digits).sum()) + extra
-        self.out = torch.zeros(max(out_size, 1), dtype=torch.uint8, device=device)
+        # [front: guard rounded up to 256 B, + out_shift][out_size bytes][guard]; front and back hold GUARD_BYTE
+        self.guard = guard
+        self.front = ((guard + 255) & ~255) + out_shift
+        self.buf = torch.zeros(self.front + max(out_size, 1) + guard, dtype=torch.uint8, device=device)
+        if self.front:
+            self.buf[: self.front] = self.GUARD_BYTE
+        if guard:
+            self.buf[self.front + out_size:] = self.GUARD_BYTE
+        self.out = self.buf[self.front: self.front + max(out_size, 1)]
         self.out_size = out_size
         self.work = torch.zeros((self.n + 4095) // 4096 + 1, dtype=torch.int64, device=device)
 
     def desc(self) -> RespBatch:
-        return RespBatch(self.arena.data_ptr(), self.resps.data_ptr(),
+        return RespBatch(self.arena.data_ptr() + self.arena_shift, self.resps.data_ptr(),
                          self.fields.data_ptr() if self.fields is not None else None, self.n, len(self.date),
-                         self.date, self.out_off.data_ptr(), self.out.data_ptr(), self.out_size,
-                         self.work.data_ptr())
+                         self.date, self.out_off.data_ptr(), self.out.data_ptr() if self.out_size else None,
+                         self.out_size, self.work.data_ptr())
 
     def launch(self, stream=None) -> None:
         import torch
@@ -734,10 +809,15 @@ class DeviceResponses:
             raise RuntimeError(f"rhp_write_responses failed: {rc}")
 
     def result(self):
+        """(bytes, offsets[n + 1]); with a guard, also the guard bytes before and after `out`"""
         import torch
         torch.cuda.synchronize()
         off = self.out_off.cpu().numpy().view(np.uint64)
-        return self.out.cpu().numpy()[: int(off[-1])], off
+        buf = self.buf.cpu().numpy()
+        out = buf[self.front: self.front + self.out_size][: int(off[-1])]
+        if not self.guard:
+            return out, off
+        return out, off, buf[self.front - self.guard: self.front], buf[self.front + self.out_size:]
 
 
 def write_responses(arena: np.ndarray, resps: np.ndarray, fields: np.ndarray, date: bytes = DEFAULT_DATE):

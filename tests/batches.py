@@ -84,6 +84,34 @@ def long_batch():
     ]
 
 
+HTTP_LIMIT_METHODS, HTTP_LIMIT_NAMES, HTTP_LIMIT_VALUES = (3, 255, 256), (1, 62, 63, 64), (1, 1007, 1008, 1023, 1024)
+
+
+def http_field_limits():
+    """http-mode requests at the limits of the dense encodings (include/rhp.h):
+    a dense request record holds a method of at most 255 bytes; a u16 header
+    record holds a name of at most 62 and a value of at most 1007 bytes
+    (RHP_DENSE_NAME_MAX, RHP_DENSE_VALUE_MAX; 63 | 1023 << 6 is the overflow
+    mark), and its bit fields end at 63 and 1023, so lengths on either side of
+    both ends are here.  One head per (method, name, value) length, five
+    requests of each: no body, a Content-Length body, the same two bytes short
+    (result 0), a chunked body, and a POST whose Content-Length field stands
+    before the long field."""
+    cl, ch = b"Content-Length: 5\r\n", b"Transfer-Encoding: chunked\r\n"
+    out = []
+    for m in HTTP_LIMIT_METHODS:
+        for nl in HTTP_LIMIT_NAMES:
+            for vl in HTTP_LIMIT_VALUES:
+                field = b"N" * nl + b": " + b"v" * vl + b"\r\n"
+                head = b"M" * m + b" /p HTTP/1.1\r\n" + field
+                out += [head + b"\r\n",
+                        head + cl + b"\r\nhello",
+                        head + cl + b"\r\nhel",
+                        head + ch + b"\r\n5\r\nhello\r\n3\r\nabc\r\n0\r\n\r\n",
+                        b"POST /p HTTP/1.1\r\n" + cl + field + b"\r\nhello"]
+    return out
+
+
 BUILDERS = {"long_batch": long_batch, "edge": lambda: EDGE * 3, "dense": lambda: dense_header_batch(2000, 21)}
 
 

@@ -26,7 +26,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import libreactorng_amd as rhp  # noqa: E402
 from oracle_util import reference_write_responses  # noqa: E402
 
-SETS = [("plaintext", 4096, 1), ("mixed", 2000, 7), ("mixed", 2000, 0x5EED0006)]
+SETS = [("plaintext", 4096, 1), ("mixed", 2000, 7), ("mixed", 2000, 0x5EED0006),
+        ("edge", 4097, 0x5EED0007), ("edge-coop", 1000, 0x5EED0008)]
 
 
 def sha(*arrays) -> str:

@@ -7,11 +7,14 @@ parsed a request.
 
 CPU: the kernel's emulator and the product's exact parser in the dense layouts;
 a method over 255 bytes sends a request to the exact path, a header name of 63+
-or a value of 1008+ bytes overflows into the u32 area.
-GPU (-m gpu): the DFA kernel (both loop forms) and the exact kernel in the dense
+or a value of 1008+ bytes overflows into the u32 area; the same limits in http
+mode (batches.http_field_limits) in the dense, compact and request-major
+layouts and through rhp_cpu_pack_dense.
+GPU (-m gpu): that http batch by every kernel at every alignment; the DFA kernel (both loop forms) and the exact kernel in the dense
 layout, against the golden sets, fuzz at every max_headers, the full-size
 digests of configs 2/3/4, edge cases at every alignment, last_len; the
 DFA/exact choice equals the emulator's."""
+import functools
 import hashlib
 import json
 import os
@@ -22,7 +25,7 @@ import pytest
 import libreactorng_amd as rhp
 from golden_sets import inputs, record_digest
 from oracle_util import assert_same, canon, run_oracle, to_rhp
-from batches import EDGE, pack
+from batches import EDGE, HTTP_LIMIT_NAMES, HTTP_LIMIT_VALUES, http_field_limits, pack
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SETS = json.load(open(os.path.join(GOLDEN, "manifest.json")))["sets"]
@@ -108,6 +111,60 @@ def test_emulation_dense_http_matches_golden(name):
         assert_same(canon(res, spec["mode"]), want, buf, off, f"dense http vs golden {name}")
         if "bytes_out_sha256" in z.files:
             assert hashlib.sha256(res.bytes_out.tobytes()).digest() == z["bytes_out_sha256"].tobytes()
+
+
+HTTP_LAYS = [rhp.LAYOUT_DENSE, rhp.LAYOUT_COMPACT, rhp.LAYOUT_REQUEST_MAJOR]
+LIMIT_SHIFTS, LIMIT_MAXH = (0, 1, 2, 3), (1, 2, 16)
+
+
+@functools.lru_cache(maxsize=None)
+def http_limits(shift, maxh, times=1):
+    """(buf, off, the oracle's canonical records, its de-framed bytes) of
+    batches.http_field_limits(); shared, never written"""
+    buf, off = pack(http_field_limits() * times, align_shift=shift)
+    rq, hd, ht, out = run_oracle(buf, off, maxh, rhp.MODE_HTTP)
+    for a in (buf, off, out):
+        a.flags.writeable = False
+    return buf, off, to_rhp(rq, hd, ht, rhp.MODE_HTTP), out
+
+
+def check_http_limits(res, shift, maxh, times, label):
+    buf, off, want, out = http_limits(shift, maxh, times)
+    assert_same(canon(res, rhp.MODE_HTTP), want, buf, off, label)
+    assert (res.bytes_out == out).all(), f"{label}: de-framed bytes differ from the oracle's"
+
+
+@pytest.mark.parametrize("maxh", LIMIT_MAXH)
+@pytest.mark.parametrize("shift", LIMIT_SHIFTS)
+def test_dense_http_field_limits(shift, maxh):
+    """http mode at the limits of the dense encodings (method 255/256, name
+    62/63/64, value 1007/1008/1023/1024 bytes): the emulator in the layouts the
+    product ships and the exact parser equal the oracle, the de-framed bytes
+    included; rhp_cpu_pack_dense rebuilds the records of the requests it calls
+    dense, and calls some but not all of them dense."""
+    buf, off, want, _ = http_limits(shift, maxh)
+    n = len(off) - 1
+    assert n == 300
+    for lay in HTTP_LAYS:
+        res, _ = rhp.emulate(buf, off, maxh, rhp.MODE_HTTP, lay)
+        check_http_limits(res, shift, maxh, 1, f"http limits (emulation, layout {lay}) shift{shift} maxh{maxh}")
+        if lay == D:
+            flags, _ = dense_fields(res, n)
+            wide = (flags & rhp.DENSE_WIDE) != 0
+            assert wide.any() and not wide.all()
+            m256 = np.array([r.startswith(b"M" * 256) for r in http_field_limits()])
+            assert wide[m256 & (want[2]["result"] == 1)].all()   # a method the u8 cannot hold: the exact path
+        res = rhp.parse_cpu_exact(buf, off, maxh, rhp.MODE_HTTP, lay)
+        check_http_limits(res, shift, maxh, 1, f"http limits (CPU exact, layout {lay}) shift{shift} maxh{maxh}")
+    res = rhp.parse_cpu_exact(buf, off, maxh, rhp.MODE_HTTP)
+    assert 0 < check_pack(res, n, maxh) < n
+    # parsed with room for its fields, each length is where the encodings say
+    if maxh == 16:
+        ok = want[2]["result"] == 1
+        assert ok.sum() == 240
+        assert set(want[0]["method_len"][ok]) == {3, 4, 255, 256}
+        assert set(HTTP_LIMIT_NAMES) <= set(want[1]["name_len"][ok].ravel())
+        assert set(HTTP_LIMIT_VALUES) <= set(want[1]["value_len"][ok].ravel())
 
 
 def test_dense_sizes():
@@ -218,6 +275,35 @@ def test_gpu_dense_http_fuzz_vs_oracle(maxh):
     assert np.array_equal(res.reqs["flags"] & (rhp.F_EXACT | rhp.F_WIDE), emu.reqs["flags"] & (rhp.F_EXACT | rhp.F_WIDE))
 
 
+@functools.lru_cache(maxsize=None)
+def http_limits_emulated_flags(shift, maxh, lay, times):
+    """(F_EXACT | F_WIDE of the expanded records, the raw dense flag bytes) of the emulator"""
+    buf, off, _, _ = http_limits(shift, maxh, times)
+    emu, _ = rhp.emulate(buf, off, maxh, rhp.MODE_HTTP, lay)
+    return emu.reqs["flags"] & (rhp.F_EXACT | rhp.F_WIDE), dense_fields(emu, len(off) - 1)[0].copy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lay", HTTP_LAYS)
+@pytest.mark.parametrize("impl", IMPLS)
+@pytest.mark.parametrize("maxh", LIMIT_MAXH)
+@pytest.mark.parametrize("shift", LIMIT_SHIFTS)
+def test_gpu_dense_http_field_limits(shift, maxh, impl, lay):
+    """batches.http_field_limits() x 20 (6000 requests, several workgroups) in
+    http mode: records and de-framed bytes equal the oracle's in the layouts the
+    product ships (dense: config 5; compact; request-major: the reactor, packed
+    by rhp_pack_dense), by every kernel; the DFA kernel's choice of path (and in
+    the dense layout its flag bytes) equals the emulator's."""
+    buf, off, _, _ = http_limits(shift, maxh, 20)
+    res = rhp.parse_batch(buf, off, maxh, rhp.MODE_HTTP, impl=impl, layout=lay)
+    check_http_limits(res, shift, maxh, 20, f"GPU http limits impl{impl} layout{lay} shift{shift} maxh{maxh}")
+    if impl != rhp.IMPL_EXACT:
+        want_flags, want_dense = http_limits_emulated_flags(shift, maxh, lay, 20)
+        assert np.array_equal(res.reqs["flags"] & (rhp.F_EXACT | rhp.F_WIDE), want_flags)
+        if lay == D:
+            assert np.array_equal(dense_fields(res, len(off) - 1)[0], want_dense)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["config5_post1k_http_h16", "chunked_post_http_h16"])
 def test_gpu_dense_http_full_size_matches_reference_digest(name):
@@ -273,12 +359,18 @@ def check_pack(res, n, maxh):
     return dense
 
 
-@pytest.mark.parametrize("name", HTTP_SETS)
+@pytest.mark.parametrize("name", HTTP_SETS + ["limits"])
 def test_pack_dense_cpu_rebuilds_records(name):
-    spec, buf, off, _ = golden(name)
-    n, maxh = len(off) - 1, spec["max_headers"]
+    if name == "limits":   # batches.http_field_limits(): names and values on both sides of what lens16 holds
+        buf, off, _, _ = http_limits(0, 16)
+        n, maxh = len(off) - 1, 16
+    else:
+        spec, buf, off, _ = golden(name)
+        n, maxh = len(off) - 1, spec["max_headers"]
     res = rhp.parse_cpu_exact(buf, off, maxh, rhp.MODE_HTTP)
     dense = check_pack(res, n, maxh)
+    if name == "limits":
+        assert 0 < dense < n   # (all wide would rebuild nothing)
     assert dense > 0 or "chunked" in name   # (every chunked body de-framed: all wide)
 
 
@@ -300,7 +392,7 @@ def test_pack_dense_cpu_fixup_chunked_stays_wide():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", ["golden", "post", "chunked", "fuzz"])
+@pytest.mark.parametrize("case", ["golden", "post", "chunked", "fuzz", "limits"])
 def test_gpu_pack_dense_equals_cpu_pack(case):
     """rhp_pack_dense on the device's records, byte for byte the CPU pack of
     the same records (their parity with the oracle is the other tests')"""
@@ -309,6 +401,9 @@ def test_gpu_pack_dense_equals_cpu_pack(case):
     if case == "golden":
         spec, buf, off, _ = golden([s for s in HTTP_SETS if "chunked" not in s][0])
         maxh = spec["max_headers"]
+    elif case == "limits":
+        buf, off, _, _ = http_limits(1, 16, 20)
+        maxh = 16
     else:
         gen = {"post": rhp.GEN_POST1K, "chunked": rhp.GEN_CHUNKED, "fuzz": rhp.GEN_FUZZ_HTTP}[case]
         buf, off = rhp.generate(gen, 20000, 77, lo=1000 if case != "fuzz" else 0)
@@ -334,3 +429,5 @@ def test_gpu_pack_dense_equals_cpu_pack(case):
     assert (got_l.reshape(maxh, n)[used] == want_l.reshape(maxh, n)[used]).all()
     dense = check_pack(res, n, maxh)
     assert dense > 0 if case != "chunked" else dense == 0   # (de-framed chunked bodies: all wide)
+    if case == "limits":
+        assert 0 < dense < n   # (all wide would compare nothing)

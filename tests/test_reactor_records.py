@@ -9,7 +9,9 @@ front, one request at a time, exactly as the reference's loop consumes it:
 result 1 -> the request, advance by `consumed`; 0 -> wait (the tail gets no
 answer); -1 -> the connection closes.  The streams mix pipelined GETs,
 Content-Length and chunked bodies (de-framed in place), LF-only line ends,
-HTTP/1.0, a request at the 16-field limit and bodies larger than a chunk.
+HTTP/1.0, a request at the 16-field limit and bodies larger than a chunk;
+stream_wide has the requests whose record slots the dense copy-back
+(RHP_REACTOR_PACK, reactor/batch.c) leaves wide, run with and without it.
 Host parsers on CPU; the MI355X batch parser (asynchronous rounds) on the GPU.
 """
 import os
@@ -43,6 +45,29 @@ def stream_mixed(seed=7):
               b"\r\n0\r\n\r\n"]
     parts += [b"GET /t%d HTTP/1.1\r\nX-I: %d\r\n\r\n" % (i, i) for i in range(20)]
     parts += [b"GET /last HTTP/1.1\r\nHost:"]   # incomplete: no answer
+    return b"".join(parts)
+
+
+def stream_wide():
+    """Requests whose record slots rhp_pack_dense must leave wide for a length
+    (name over 62, value over 1007, method over 255 bytes: include/rhp.h) or
+    because the DFA hands them to the exact parser (leading CRLF, no space
+    after the colon, trailing OWS, obs-fold), beside ones just inside each
+    limit, canonical GETs around each, a chunked POST and an incomplete tail:
+    the server reads a wide slot's request-major records end to end."""
+    get = b"GET /g HTTP/1.1\r\nHost: a\r\n\r\n"
+    rest = [b"GET /n%d HTTP/1.1\r\n" % k + b"N" * k + b": v\r\nHost: a\r\n\r\n" for k in (62, 63, 100)]
+    rest += [b"GET /v%d HTTP/1.1\r\nHost: a\r\nX: " % k + b"v" * k + b"\r\n\r\n" for k in (1007, 1008, 1023, 1024, 1500)]
+    rest += [b"M" * k + b" /m HTTP/1.1\r\nHost: a\r\n\r\n" for k in (255, 256)]
+    rest += [b"\r\nGET /crlf HTTP/1.1\r\nHost: a\r\n\r\n",
+             b"GET /nospace HTTP/1.1\r\nHost:x\r\n\r\n",
+             b"GET /ows HTTP/1.1\r\nHost: a \t \r\nB: c\r\n\r\n",
+             b"GET /fold HTTP/1.1\r\nA: b\r\n \tfolded\r\nHost: a\r\n\r\n",
+             b"POST /c HTTP/1.1\r\nTransfer-Encoding: chunked\r\n\r\n5\r\nhello\r\n6\r\n world\r\n0\r\n\r\n"]
+    parts = [get]
+    for r in rest:
+        parts += [r, get, TFB]
+    parts += [b"GET /last HTTP/1.1\r\nX: " + b"v" * 1100]   # incomplete: no answer
     return b"".join(parts)
 
 
@@ -98,11 +123,12 @@ def decode_echoes(raw: bytes):
     return out
 
 
-def run_echo(tmp_path, stream: bytes, chunk: int, parser: str, writer: str = "host"):
+def run_echo(tmp_path, stream: bytes, chunk: int, parser: str, writer: str = "host", env=None):
+    """env: further environment variables of the server (e.g. RHP_REACTOR_PACK)"""
     src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
     src.write_bytes(stream)
     p = subprocess.run([ECHO, str(src), str(chunk), str(dst)],
-                       env=dict(os.environ, RHP_REACTOR_PARSER=parser, RHP_REACTOR_WRITER=writer),
+                       env=dict(os.environ, RHP_REACTOR_PARSER=parser, RHP_REACTOR_WRITER=writer, **(env or {})),
                        capture_output=True, text=True, timeout=120)
     assert p.returncode == 0 and "OK" in p.stdout, p.stdout + p.stderr
     assert f"parser: {parser}" in p.stdout
@@ -110,7 +136,12 @@ def run_echo(tmp_path, stream: bytes, chunk: int, parser: str, writer: str = "ho
 
 
 CASES = [("mixed", stream_mixed, 1 << 20), ("mixed", stream_mixed, 1000), ("mixed", stream_mixed, 61),
-         ("mixed", stream_mixed, 7), ("bad", stream_bad, 1 << 20), ("bad", stream_bad, 50)]
+         ("mixed", stream_mixed, 7), ("bad", stream_bad, 1 << 20), ("bad", stream_bad, 50),
+         ("wide", stream_wide, 1 << 20), ("wide", stream_wide, 1000), ("wide", stream_wide, 61)]
+# the copy-back of the asynchronous parsers (reactor/batch.c): "1" the dense copies of
+# rhp_pack_dense / rhp_cpu_pack_dense (the default), "0" the request-major records
+PACK_CASES = [(name, make, chunk, pack) for name, make, chunk in CASES if name == "wide" for pack in ("0", "1")]
+PACK_CASES += [("mixed", stream_mixed, 1000, "0")]
 
 
 def check_echoes(got, want, name, chunk):
@@ -145,6 +176,51 @@ def test_server_records_gpu_match_oracle_sequential_loop(tmp_path, name, make, c
     reference does, or by rhp_write_responses once per round."""
     s = make()
     check_echoes(run_echo(tmp_path, s, chunk, "gpu", writer), oracle_sequential(s), name, chunk)
+
+
+@pytest.mark.parametrize("name,make,chunk,pack", PACK_CASES)
+def test_server_records_pack_modes(tmp_path, name, make, chunk, pack):
+    """host-async (the gpu parser's protocol on the CPU) with and without the dense copy-back"""
+    s = make()
+    want = oracle_sequential(s)
+    assert len(want) >= 30
+    check_echoes(run_echo(tmp_path, s, chunk, "host-async", env={"RHP_REACTOR_PACK": pack}), want, name, chunk)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,make,chunk,pack", PACK_CASES)
+def test_server_records_gpu_pack_modes(tmp_path, name, make, chunk, pack):
+    s = make()
+    check_echoes(run_echo(tmp_path, s, chunk, "gpu", env={"RHP_REACTOR_PACK": pack}), oracle_sequential(s), name, chunk)
+
+
+def test_stream_wide_slots():
+    """stream_wide is what it says: every request is answered, and parsed as
+    one batch, rhp_cpu_pack_dense leaves the slots named in its docstring wide
+    and packs the ones inside the limits"""
+    s = stream_wide()
+    want = oracle_sequential(s)
+    targets = [t for _, t, _, _ in want]
+    for t in (b"/n62", b"/n63", b"/n100", b"/v1007", b"/v1008", b"/v1023", b"/v1024", b"/v1500", b"/m", b"/crlf",
+              b"/nospace", b"/ows", b"/fold", b"/c"):
+        assert t in targets, t
+    assert b"/last" not in targets
+    assert {len(m) for m, _, _, _ in want} >= {3, 255, 256}
+    buf, off, sess, _ = rhp.pack_sessions([s])
+    res, sres, starts = rhp.fixup_cpu(buf, off, sess, 16)
+    n = len(off) - 1
+    assert int(sres[0]["n_slots"]) == len(want) + 1   # (the incomplete tail's slot: result 0)
+    assert (res.http["result"][: len(want)] == 1).all() and res.http["result"][len(want)] == 0
+    dreq, _, _ = rhp.pack_dense_cpu(res, n, 16)
+    wide = {}
+    for i in range(len(want)):
+        r = res.reqs[i]
+        if res.http[i]["result"] == 1 and r["ret"] > 0:
+            a = int(starts[i]) + int(r["path_off"])
+            wide.setdefault(bytes(buf[a: a + int(r["path_len"])]), bool(dreq[8 * i + 7] & rhp.DENSE_WIDE))
+    for t, w in ((b"/n62", False), (b"/n63", True), (b"/n100", True), (b"/v1007", False), (b"/v1008", True),
+                 (b"/v1023", True), (b"/v1024", True), (b"/v1500", True), (b"/g", False), (b"/plaintext", False)):
+        assert wide[t] == w, (t, wide)
 
 
 def stream_posts():
