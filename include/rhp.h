@@ -83,8 +83,9 @@ enum rhp_layout {
   RHP_LAYOUT_HEADER_MAJOR = 1,
   RHP_LAYOUT_COMPACT = 2,     /* 4-byte header records, below (http mode: 8-byte http records too;
                                  not with RHP_BATCH_SPECULATIVE) */
-  RHP_LAYOUT_DENSE = 3,       /* RHP_MODE_PHR: 8-byte request and 2-byte header records, below */
-  RHP_LAYOUT_DENSE_RM = 4     /* the same, the header records request-major */
+  RHP_LAYOUT_DENSE = 3,       /* 8-byte request and 2-byte header records, below (both modes; http
+                                 mode: the 8-byte http records too; not with RHP_BATCH_SPECULATIVE) */
+  RHP_LAYOUT_DENSE_RM = 4     /* the same, the header records request-major (RHP_MODE_PHR only) */
 };
 /* Compact records (RHP_LAYOUT_COMPACT).  A header line the DFA
  * parses is `name ": " value CRLF` and the first one starts right after the
@@ -103,9 +104,10 @@ enum rhp_layout {
  * 2: 48 -> 32 B per request with the 16-B request record). */
 #define RHP_COMPACT_WIDE_OFF(n, m) ((((size_t) (n) * (size_t) (m) * 4u) + 15u) & ~(size_t) 15u)
 #define RHP_COMPACT_HDRS_BYTES(n, m) (RHP_COMPACT_WIDE_OFF(n, m) + (size_t) (n) * (size_t) (m) * 8u)
-/* Dense records (RHP_LAYOUT_DENSE / RHP_LAYOUT_DENSE_RM, RHP_MODE_PHR; round
- * 6).  The compact layout's running-sum offsets with narrower fields, for the
- * DFA's records.  reqs holds rhp_req_dense_t dreq[n] (8 B) and, at byte
+/* Dense records (RHP_LAYOUT_DENSE in both modes, RHP_LAYOUT_DENSE_RM in
+ * RHP_MODE_PHR; round 6).  The compact layout's running-sum offsets with
+ * narrower fields, for the DFA's records.  In RHP_MODE_HTTP the http records
+ * of a dense batch are the compact ones (rhp_http_compact_t, below).  reqs holds rhp_req_dense_t dreq[n] (8 B) and, at byte
  * RHP_DENSE_REQ_WIDE_OFF(n), a wide area rhp_req_t wide[n]
  * (RHP_DENSE_REQS_BYTES(n) bytes in all).  hdrs holds u16 lens, name_len |
  * value_len << 6, at index k * n + i (RHP_LAYOUT_DENSE, header-major) or
@@ -154,7 +156,7 @@ typedef struct rhp_http {
   uint64_t body_len;
 } rhp_http_t;
 
-/* Compact http records (RHP_LAYOUT_COMPACT, RHP_MODE_HTTP): http holds
+/* Compact http records (RHP_LAYOUT_COMPACT and RHP_LAYOUT_DENSE, RHP_MODE_HTTP): http holds
  * rhp_http_compact_t hc[n] (8 B) and, at byte RHP_COMPACT_HTTP_WIDE_OFF(n), a
  * wide area rhp_http_t wide[n]; RHP_COMPACT_HTTP_BYTES(n) bytes in all.  A
  * record without RHP_HTTP_WIDE holds result, body_kind and body_len, and
@@ -189,13 +191,13 @@ typedef struct rhp_batch {
   uint32_t        max_headers; /* headers capacity per request (*num_headers in) */
   uint32_t        mode;        /* enum rhp_mode */
   uint32_t        layout;      /* enum rhp_layout: where record k of request i lives in hdrs */
-  rhp_req_t      *reqs;        /* device [n] (RHP_LAYOUT_DENSE: RHP_DENSE_REQS_BYTES(n) bytes,
+  rhp_req_t      *reqs;        /* device [n] (RHP_LAYOUT_DENSE / _DENSE_RM: RHP_DENSE_REQS_BYTES(n) bytes,
                                   rhp_req_dense_t and the wide area) */
   rhp_hdr_t      *hdrs;        /* device [n * max_headers] records, laid out as `layout` says
                                   (n * max_headers < 2^32); RHP_LAYOUT_COMPACT:
                                   RHP_COMPACT_HDRS_BYTES(n, max_headers) bytes; RHP_LAYOUT_DENSE:
                                   RHP_DENSE_HDRS_BYTES(n, max_headers) bytes */
-  rhp_http_t     *http;        /* device [n], RHP_MODE_HTTP (RHP_LAYOUT_COMPACT:
+  rhp_http_t     *http;        /* device [n], RHP_MODE_HTTP (RHP_LAYOUT_COMPACT and RHP_LAYOUT_DENSE:
                                   RHP_COMPACT_HTTP_BYTES(n) bytes, rhp_http_compact_t) */
   uint32_t       *work;        /* reserved, may be NULL (device scratch of RHP_WORK_WORDS u32
                                   for future kernels; the current ones keep their scheduling
@@ -352,6 +354,75 @@ typedef struct rhp_resp_batch {
 /* Launch status as rhp_parse_batch; four kernels on `stream` (sizes with tile
  * sums, two scan passes, copy). */
 int rhp_write_responses(const rhp_resp_batch_t *batch, void *stream);
+
+/*
+ * Batched header lookup and route match: what a server does between
+ * http_read_request and http_write_response, for a parsed batch whose bytes and
+ * records stay in HBM.
+ *   string_t http_field_lookup(http_field_t *, size_t, string_t name);
+ *                       src/reactor/http.c:167-175 (decl http.h:35): the value of
+ *                       the first field whose name is string_equal_case to `name`
+ *                       (equal sizes and gnulib memcasecmp, src/reactor/data.c:11-28,
+ *                       string.c), string_null() when there is none
+ *   string_equal(request.method / request.target, ...)
+ *                       the dispatch of the reference's users (http.c:198,
+ *                       test/server.c:75-82): equal sizes and memcmp
+ * For request i of a batch that rhp_parse_batch has parsed on `stream`, in any
+ * record layout and either mode the parser accepts (the combinations it
+ * refuses are refused here with the same code):
+ *   a request is "ready" when ret > 0 (RHP_MODE_PHR; RHP_RET_TOOLONG is not) or
+ *   result == 1 (RHP_MODE_HTTP);
+ *   fields[j * n + i] is the value span (offsets from the request's start, as
+ *   rhp_hdr_t) of the first header record k < num_headers whose name is not
+ *   NULL (an obs-fold line never matches), has the length of name j and equals
+ *   it byte for byte after both sides' ASCII a..z are mapped to A..Z (the C
+ *   locale's toupper: no other byte is mapped, so '^' and '~', '_' and DEL, '`'
+ *   and '@' differ); a header that is present with an empty value gives
+ *   {value_off, 0}; no such header, or a request that is not ready, gives
+ *   {RHP_NAME_NULL, 0};
+ *   route[i] is the index of the first route whose target has the path's length
+ *   and bytes and whose method has the method's (a route with method.len == 0
+ *   takes any method); RHP_ROUTE_NONE when there is none or the request is not
+ *   ready.
+ * The records of a request that is not ready and those past num_headers are
+ * unspecified and are not used.  The request's bytes are read as the parse
+ * left them (http mode: through bytes_rw, after chunked bodies were de-framed
+ * in place), the name bytes only of records whose name_len is a lookup name's,
+ * as the aligned dwords that hold them.
+ * RHP_BATCH_SPECULATIVE batches are refused (-EINVAL): after
+ * rhp_fixup_sessions a slot's offsets are relative to req_start, not to
+ * offsets[i]; classifying those slots is a follow-up.  Also -EINVAL: an empty
+ * name or one longer than RHP_CLASSIFY_NAME_MAX, a count above its limit,
+ * route text above RHP_CLASSIFY_TEXT_MAX, n_names == 0 && n_routes == 0, a
+ * missing table or output.  n == 0 succeeds and launches nothing.
+ * Launch contract as rhp_parse_batch: asynchronous on `stream`, no allocation
+ * and no synchronisation; the host tables (text, names, routes) are copied
+ * into the launch and may be freed when the call returns; thread-safe.
+ */
+#define RHP_CLASSIFY_MAX_NAMES   16u   /* header names looked up per call */
+#define RHP_CLASSIFY_NAME_MAX    64u   /* longest lookup name, bytes; names are non-empty */
+#define RHP_CLASSIFY_MAX_ROUTES  32u
+#define RHP_CLASSIFY_TEXT_MAX  2048u   /* total bytes of all route methods + targets */
+#define RHP_ROUTE_NONE       0xFFFFu
+
+typedef struct rhp_fieldref {
+  uint16_t value_off, value_len;   /* absent: value_off == RHP_NAME_NULL, value_len == 0 */
+} rhp_fieldref_t;
+
+typedef struct rhp_route {
+  rhp_span_t method, target;       /* spans of `text`; method.len == 0: any method */
+} rhp_route_t;
+
+typedef struct rhp_classify {
+  const uint8_t     *text;      /* host: the bytes of the names and routes */
+  const rhp_span_t  *names;     /* host [n_names]: spans of `text` */
+  const rhp_route_t *routes;    /* host [n_routes], may be NULL when n_routes == 0 */
+  uint32_t           n_names, n_routes;
+  rhp_fieldref_t    *fields;    /* device [n_names * n], name-major: fields[j * n + i] */
+  uint16_t          *route;     /* device [n]; may be NULL when n_routes == 0 */
+} rhp_classify_t;
+
+int rhp_classify_batch(const rhp_batch_t *batch, const rhp_classify_t *c, void *stream);
 
 
 #ifdef __cplusplus

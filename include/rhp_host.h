@@ -11,6 +11,8 @@
  *   rhp_expand_records    any layout's header records (the compact and dense
  *                         ones included) as rhp_hdr_t, on the host;
  *   rhp_expand_reqs       the dense layout's request records as rhp_req_t
+ *   rhp_cpu_classify_batch  rhp_classify_batch (rhp.h) over a parsed batch in
+ *                         host memory, written over the three rhp_expand_*
  *
  *   rhp_phr_parse_request the same exact parser with phr_parse_request's own
  *                         signature and outputs (pointers into buf, no length
@@ -42,6 +44,11 @@ int rhp_emu_parse_batch(const rhp_batch_t *batch, uint64_t *stats);
  * (the reactor's host-async parser exercises the dense copy-back with it) */
 int rhp_cpu_pack_dense(const rhp_batch_t *batch, rhp_req_dense_t *dreq, rhp_http_compact_t *hc, uint16_t *lens16);
 
+/* rhp_classify_batch (rhp.h) on the host: `batch` is a parsed batch whose
+ * pointers, and c->fields and c->route, are host memory.  The same results
+ * and the same -22 for refused arguments (the GPU tests compare the two). */
+int rhp_cpu_classify_batch(const rhp_batch_t *batch, const rhp_classify_t *c);
+
 /* A parsed batch's header records as rhp_hdr_t, out[i * max_headers + k]
  * (request-major), from host copies of its reqs and hdrs in the batch's
  * layout; records past num_headers and those of requests with ret <= 0 are
@@ -57,7 +64,7 @@ int rhp_expand_records(const rhp_batch_t *batch, const rhp_req_t *reqs, const vo
  * requests first: rhp_expand_records and rhp_expand_http take rhp_req_t. */
 int rhp_expand_reqs(const rhp_batch_t *batch, const void *reqs, rhp_req_t *out);
 /* A batch's http records (RHP_MODE_HTTP) as rhp_http_t[n]: copied, or for
- * RHP_LAYOUT_COMPACT expanded from the compact records and their wide area
+ * RHP_LAYOUT_COMPACT and RHP_LAYOUT_DENSE expanded from the compact records and their wide area
  * (rhp.h rhp_http_compact_t; consumed from reqs[i].ret).  0, or -22. */
 int rhp_expand_http(const rhp_batch_t *batch, const rhp_req_t *reqs, const void *http, rhp_http_t *out);
 

@@ -65,11 +65,11 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 
 # exported C-ABI symbols of librhp.so, as declared in include/rhp.h
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
-               "rhp_fixup_sessions", "rhp_pack_dense")
+               "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
-                "rhp_test_chunk_window",
+                "rhp_cpu_classify_batch", "rhp_test_chunk_window",
                 "rhp_test_chunk_exact")
 
 _rhp = None
@@ -85,6 +85,18 @@ class RespBatch(ctypes.Structure):
 
 
 RHP_DATE_LEN = 29
+
+
+class Classify(ctypes.Structure):
+    """rhp_classify_t (include/rhp.h): header lookup and route match over a parsed batch"""
+    _fields_ = [("text", ctypes.c_void_p), ("names", ctypes.c_void_p), ("routes", ctypes.c_void_p),
+                ("n_names", ctypes.c_uint32), ("n_routes", ctypes.c_uint32), ("fields", ctypes.c_void_p),
+                ("route", ctypes.c_void_p)]
+
+
+CLASSIFY_MAX_NAMES, CLASSIFY_NAME_MAX, CLASSIFY_MAX_ROUTES, CLASSIFY_TEXT_MAX = 16, 64, 32, 2048
+ROUTE_NONE = 0xFFFF
+FIELDREF_DTYPE = np.dtype([("value_off", "<u2"), ("value_len", "<u2")])   # absent: (RHP_NAME_NULL, 0)
 
 
 def _torch_hip_runtime() -> str | None:
@@ -152,6 +164,8 @@ def lib() -> ctypes.CDLL:
         vp = ctypes.c_void_p
         _rhp.rhp_pack_dense.argtypes = [ctypes.POINTER(Batch), vp, vp, vp, vp]
         _rhp.rhp_pack_dense.restype = ctypes.c_int
+        _rhp.rhp_classify_batch.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Classify), vp]
+        _rhp.rhp_classify_batch.restype = ctypes.c_int
     return _rhp
 
 
@@ -190,6 +204,8 @@ def host() -> ctypes.CDLL:
         _host.rhp_cpu_pack_dense.restype = ctypes.c_int
         _host.rhp_expand_reqs.restype = ctypes.c_int
         _host.rhp_expand_http.restype = ctypes.c_int
+        _host.rhp_cpu_classify_batch.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Classify)]
+        _host.rhp_cpu_classify_batch.restype = ctypes.c_int
     return _host
 
 
@@ -273,6 +289,9 @@ class Result:
     raw_hdrs: np.ndarray | None = None   # the hdrs buffer as the parser left it (its layout's bytes)
     raw_http: np.ndarray | None = None   # the http buffer as the parser left it (compact: rhp_http_compact_t)
     raw_reqs: np.ndarray | None = None   # the reqs buffer as the parser left it (dense: rhp_req_dense_t + wide)
+    batch: Batch | None = None           # the parsed batch over host memory (bytes, offsets, the raw records):
+    #                                      what classify_cpu reads; `keep` holds the arrays it points into
+    keep: tuple = ()
 
 
 def canonical(res: Result, mode: int):
@@ -421,6 +440,7 @@ def _host_batch(buf, off, max_headers, mode, layout=LAYOUT_REQUEST_MAJOR, last_l
     res.raw_reqs = raw_reqs
     res.raw_hdrs = raw   # the compact layout's records are expanded once the parse has run (_host_done)
     res.raw_http = raw_http if mode == MODE_HTTP else None
+    res.batch, res.keep = b, (rw, off, raw_reqs, raw, raw_http)
     return b, res
 
 
@@ -472,6 +492,7 @@ class DeviceBatch:
         self.mode = mode
         self.layout = layout
         self.flags = flags
+        self.host_buf, self.host_off = buf, off   # (references: result() describes the parsed batch over them)
         self.bytes = torch.from_numpy(buf).to(device)
         self.offsets = torch.from_numpy(off.view(np.int64)).to(device)
         self.reqs = torch.zeros(max(reqs_bytes(self.n, layout), 8), dtype=torch.uint8, device=device)
@@ -512,7 +533,46 @@ class DeviceBatch:
         raw_http = self.http.cpu().numpy() if self.mode == MODE_HTTP else None
         http = expand_http(reqs, raw_http, self.n, self.layout) if self.mode == MODE_HTTP else None
         out = self.bytes.cpu().numpy() if self.mode == MODE_HTTP else None
-        return Result(reqs, hdrs, http, out, raw, raw_http, raw_reqs)
+        res = Result(reqs, hdrs, http, out, raw, raw_http, raw_reqs)
+        hb = out if out is not None else self.host_buf   # the bytes as the parse left them
+        res.batch = Batch(_ptr(hb), _ptr(hb), _ptr(self.host_off), hb.size, self.n, self.max_headers, self.mode,
+                          self.layout, _ptr(raw_reqs), _ptr(raw), _ptr(raw_http) if raw_http is not None else None,
+                          None, self.flags, 0, None)
+        res.keep = (hb, self.host_off, raw_reqs, raw, raw_http)
+        return res
+
+    def classifier(self, names, routes=()):
+        """rhp_classify_batch over this batch, prepared once: (launch(stream=None),
+        fields tensor u8 [n_names * n * 4], route tensor i16 [n] or None).  Each
+        launch() is one asynchronous call on the stream (default: the current one)."""
+        import torch
+        text, nm, rt = classify_tables(names, routes)
+        dev = self.reqs.device
+        fields = torch.zeros(max(len(nm) * self.n, 1) * FIELDREF_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        route = torch.zeros(max(self.n, 1), dtype=torch.int16, device=dev) if len(rt) else None
+        c = Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm), len(rt),
+                     fields.data_ptr() if len(nm) else None, route.data_ptr() if route is not None else None)
+        d = self.desc()
+
+        def launch(stream=None, _keep=(text, nm, rt)):
+            s = stream if stream is not None else torch.cuda.current_stream()
+            rc = lib().rhp_classify_batch(ctypes.byref(d), ctypes.byref(c), ctypes.c_void_p(s.cuda_stream))
+            if rc != 0:
+                raise RuntimeError(f"rhp_classify_batch failed: {rc}")
+        return launch, fields, route
+
+    def classify(self, names, routes=(), stream=None):
+        """Header lookup and route match of the parsed batch on the GPU (after
+        launch(), on the same stream): (fields FIELDREF_DTYPE [n_names, n], route u16 [n])."""
+        import torch
+        launch, fields, route = self.classifier(names, routes)
+        launch(stream)
+        torch.cuda.synchronize()
+        n_names = len(names)
+        f = fields.cpu().numpy()[: n_names * self.n * 4].view(FIELDREF_DTYPE).reshape(n_names, self.n)
+        r = (route.cpu().numpy().view(np.uint16)[: self.n] if route is not None
+             else np.full(self.n, ROUTE_NONE, dtype=np.uint16))
+        return f, r
 
 
 def parse_batch(buf: np.ndarray, off: np.ndarray, max_headers: int = 16, mode: int = MODE_PHR,
@@ -525,6 +585,54 @@ def parse_batch(buf: np.ndarray, off: np.ndarray, max_headers: int = 16, mode: i
         return db.result()
     finally:
         lib().rhp_set_impl(IMPL_DFA)
+
+
+def classify_tables(names, routes=()):
+    """The host tables of rhp_classify_t: (text u8, names u32 [n_names, 2], routes
+    u32 [n_routes, 4]) for header names (bytes) and (method, target) routes; an
+    empty or None method takes any method."""
+    parts, at = [], 0
+
+    def span(b):
+        nonlocal at
+        b = bytes(b or b"")
+        parts.append(b)
+        at += len(b)
+        return at - len(b), len(b)
+
+    nm = np.array([span(x) for x in names], dtype=np.uint32).reshape(-1, 2)
+    rt = np.array([span(m) + span(t) for m, t in routes], dtype=np.uint32).reshape(-1, 4)
+    text = np.frombuffer(b"".join(parts) + b"\0", dtype=np.uint8).copy()
+    return text, nm, rt
+
+
+def classify_cpu(res_or_batch, names, routes=()):
+    """rhp_cpu_classify_batch (include/rhp_host.h) over a parsed batch in host
+    memory: a Result of emulate / parse_cpu_exact / parse_batch / DeviceBatch.result
+    (its `batch`), or a Batch.  Returns (fields FIELDREF_DTYPE [n_names, n], route
+    u16 [n]; RHP_ROUTE_NONE everywhere without routes)."""
+    b = res_or_batch.batch if isinstance(res_or_batch, Result) else res_or_batch
+    if b is None:
+        raise ValueError("this Result does not describe its batch")
+    text, nm, rt = classify_tables(names, routes)
+    n = b.n
+    fields = np.zeros((len(nm), n), dtype=FIELDREF_DTYPE)
+    route = np.full(n, ROUTE_NONE, dtype=np.uint16)
+    c = Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm), len(rt),
+                 _ptr(fields) if len(nm) else None, _ptr(route) if len(rt) else None)
+    rc = host().rhp_cpu_classify_batch(ctypes.byref(b), ctypes.byref(c))
+    if rc != 0:
+        raise RuntimeError(f"rhp_cpu_classify_batch failed: {rc}")
+    return fields, route
+
+
+def classify_batch(buf: np.ndarray, off: np.ndarray, names, routes=(), max_headers: int = 16, mode: int = MODE_PHR,
+                   layout: int = LAYOUT_REQUEST_MAJOR):
+    """Parse a host batch on the GPU and classify it there, on one stream (copies
+    in, two launches, copies the classification out): (fields, route) as classify_cpu."""
+    db = DeviceBatch(buf, off, max_headers, mode, layout=layout)
+    db.launch()
+    return db.classify(names, routes)
 
 
 def pack_dense_cpu(res: Result, n: int, max_headers: int):

@@ -1,0 +1,304 @@
+/*
+ * rhp_classify.hip -- rhp_classify_batch (rhp.h): http_field_lookup
+ * (src/reactor/http.c:167-175) for up to 16 names and the string_equal route
+ * dispatch of the reference's users (http.c:198, test/server.c:75-82) over a
+ * parsed batch whose bytes and records are in HBM.  gfx950.
+ *
+ * One request per lane.  The lane decodes its request record (any of the five
+ * layouts, rhp.h), walks its header records k < num_headers -- in the
+ * header-major layouts lens[k * n + i] is one coalesced load per wave and k, in
+ * the compact and dense ones the offsets are the running sum carried in
+ * registers -- and compares in two stages: name_len against the lengths of the
+ * names still looked for (records only, a 65-entry mask table in LDS), and only
+ * for a length match the name's bytes, read as the aligned dwords that hold
+ * them, funnel-shifted, folded four at a time (SWAR a..z -> A..Z) and compared
+ * with the names the host folded once.  The lookup tables travel by value in
+ * the kernel argument (3.5 KiB) and the block copies them to LDS at its start:
+ * no allocation, no copy, the caller's tables are free when the call returns.
+ *
+ * Nothing of a request that is not ready, and no record k >= num_headers, is
+ * used: those are unspecified (rhp.h) and may hold anything.
+ */
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "rhp.h"
+#include "rhp_classify_args.h"
+
+namespace {
+
+constexpr uint32_t kNameDwords = RHP_CLASSIFY_NAME_MAX / 4u;
+/* route methods and targets, each starting at a dword and zero-padded to one */
+constexpr uint32_t kTextDwords = (RHP_CLASSIFY_TEXT_MAX + 2u * RHP_CLASSIFY_MAX_ROUTES * 3u) / 4u;
+
+struct CTables {
+  uint32_t name[RHP_CLASSIFY_MAX_NAMES][kNameDwords];   /* folded to upper case, zero-padded */
+  uint32_t text[kTextDwords];
+  uint16_t r_moff[RHP_CLASSIFY_MAX_ROUTES], r_mlen[RHP_CLASSIFY_MAX_ROUTES];   /* dword index into text, bytes */
+  uint16_t r_toff[RHP_CLASSIFY_MAX_ROUTES], r_tlen[RHP_CLASSIFY_MAX_ROUTES];
+  uint8_t  name_len[RHP_CLASSIFY_MAX_NAMES];
+};
+constexpr uint32_t kTabDwords = sizeof(CTables) / 4u;
+static_assert(sizeof(CTables) % 4u == 0 && offsetof(CTables, name_len) % 4u == 0, "copied to LDS as dwords");
+
+struct CParams {
+  CTables         t;          /* first: the kernel reads it from the start of its argument segment */
+  const uint8_t  *bytes;
+  const uint64_t *offsets;
+  const uint8_t  *reqs, *hdrs, *http;
+  uint32_t       *fields;
+  uint16_t       *route;
+  uint32_t        n, m, layout, n_names, n_routes;
+};
+static_assert(offsetof(CParams, t) == 0, "the tables lead the argument");
+static_assert(sizeof(CParams) <= 4096, "a kernel argument holds 4 KiB");
+
+/* C-locale toupper of four bytes at once: a byte in 'a'..'z' (bit 7 clear,
+ * low seven bits in 0x61..0x7a) loses bit 5, every other byte stays */
+__host__ __device__ inline uint32_t fold4(uint32_t x)
+{
+  const uint32_t x7 = x & 0x7f7f7f7fu;
+  const uint32_t ge_a = x7 + 0x1f1f1f1fu, gt_z = x7 + 0x05050505u;   /* bit 7: >= 0x61, >= 0x7b (no carry out of a byte) */
+  const uint32_t is = ge_a & ~gt_z & ~x & 0x80808080u;
+  return x ^ (is >> 2);
+}
+
+/* The candidates of `cand` whose table text equals the len bytes at src:
+ * candidate j's text is tab[off(j) ...], zero-padded to a dword.  Reads the
+ * aligned dwords that hold the bytes, none past the one with the last byte,
+ * and stops at the dword that rejects the last candidate. */
+template <bool FOLD, class Off>
+__device__ __forceinline__ uint32_t same_text(const uint8_t *src, uint32_t len, uint32_t cand, const uint32_t *tab, Off off)
+{
+  if (len == 0) return cand;
+  const uintptr_t a = (uintptr_t) src;
+  const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t) 3);
+  const uint32_t sh = (uint32_t) a & 3u, nd = (sh + len + 3u) >> 2;
+  uint32_t lo = w[0];
+  for (uint32_t j = 0; j < len && cand; j += 4) {
+    const uint32_t k = (j >> 2) + 1u;
+    const uint32_t hi = k < nd ? w[k] : 0u;
+    uint32_t x = __builtin_amdgcn_alignbyte(hi, lo, sh);
+    if (len - j < 4u) x &= (1u << (8u * (len - j))) - 1u;
+    if (FOLD) x = fold4(x);
+    for (uint32_t c = cand; c; c &= c - 1u) {
+      const uint32_t q = (uint32_t) __builtin_ctz(c);
+      if (tab[off(q) + (j >> 2)] != x) cand &= ~(1u << q);
+    }
+    lo = hi;
+  }
+  return cand;
+}
+
+typedef __attribute__((address_space(4))) uint32_t ka32;   /* a dword of the kernel argument segment */
+
+__global__ __launch_bounds__(256) void rhp_classify_kernel(CParams p)
+{
+  __shared__ uint32_t tab[kTabDwords];
+  __shared__ uint16_t lenmask[RHP_CLASSIFY_NAME_MAX + 1u];
+  {
+    /* the tables lead the argument segment: read them from there (indexing
+     * the by-value struct would make a private copy per lane) */
+#if defined(__HIP_DEVICE_COMPILE__)   /* (the host pass only checks the body) */
+    const ka32 *ka = (const ka32 *) __builtin_amdgcn_kernarg_segment_ptr();
+#else
+    const ka32 *ka = nullptr;
+#endif
+    for (uint32_t t = threadIdx.x; t < kTabDwords; t += blockDim.x) tab[t] = ka[t];
+    if (threadIdx.x <= RHP_CLASSIFY_NAME_MAX) {
+      const ka32 *nl = ka + offsetof(CTables, name_len) / 4u;
+      uint32_t mk = 0;
+      for (uint32_t j = 0; j < p.n_names; j++) mk |= (((nl[j >> 2] >> (8u * (j & 3u))) & 0xffu) == threadIdx.x ? 1u : 0u) << j;
+      lenmask[threadIdx.x] = (uint16_t) mk;
+    }
+  }
+  __syncthreads();
+  const uint32_t *names = tab + offsetof(CTables, name) / 4u, *text = tab + offsetof(CTables, text) / 4u;
+  const uint16_t *r_moff = reinterpret_cast<const uint16_t *>(tab + offsetof(CTables, r_moff) / 4u);
+  const uint16_t *r_mlen = reinterpret_cast<const uint16_t *>(tab + offsetof(CTables, r_mlen) / 4u);
+  const uint16_t *r_toff = reinterpret_cast<const uint16_t *>(tab + offsetof(CTables, r_toff) / 4u);
+  const uint16_t *r_tlen = reinterpret_cast<const uint16_t *>(tab + offsetof(CTables, r_tlen) / 4u);
+
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = p.n, m = p.m;
+  if (i >= n) return;
+  const bool dense = p.layout == RHP_LAYOUT_DENSE || p.layout == RHP_LAYOUT_DENSE_RM;
+  const bool lengths = dense || p.layout == RHP_LAYOUT_COMPACT;   /* running-sum records, rhp_hdr_t ones in a wide area */
+  const bool chttp = p.layout == RHP_LAYOUT_COMPACT || p.layout == RHP_LAYOUT_DENSE;   /* rhp_http_compact_t */
+
+  /* ---- the request record: ready? path, method, num_headers, wide? ---- */
+  int32_t ret = 0;
+  uint32_t method_off = 0, method_len = 0, path_off = 0, path_len = 0, nh = 0;
+  bool wide = false;
+  {
+    bool full = !dense;   /* an rhp_req_t holds this request */
+    const uint8_t *rq = p.reqs;
+    if (dense) {
+      const uint2 d = reinterpret_cast<const uint2 *>(p.reqs)[i];
+      const uint32_t fl = d.y >> 24;
+      if (fl & RHP_DENSE_WIDE) {
+        full = true;
+        rq = p.reqs + RHP_DENSE_REQ_WIDE_OFF(n);
+      } else if (!(fl & RHP_DENSE_BAD)) {
+        ret = (int32_t) (d.x & 0xffffu);
+        path_len = d.x >> 16;
+        method_len = d.y & 0xffu;
+        path_off = method_len + 1u;
+        nh = (d.y >> 8) & 0xffu;
+      }
+    }
+    if (full) {
+      const uint4 q = reinterpret_cast<const uint4 *>(rq)[i];
+      ret = (int32_t) q.x;
+      method_len = q.y & 0xffffu;
+      path_off = q.y >> 16;
+      path_len = q.z & 0xffffu;
+      method_off = (q.z >> 16) & 0xffu;
+      nh = q.w & 0xffffu;
+      wide = lengths && (dense || ((q.w >> 16) & RHP_F_WIDE));
+    }
+  }
+  bool ready = ret > 0;   /* RHP_RET_TOOLONG is negative */
+  if (p.http) {           /* RHP_MODE_HTTP: result == 1 */
+    int32_t result;
+    if (chttp) {
+      const uint2 c = reinterpret_cast<const uint2 *>(p.http)[i];
+      if ((c.x >> 16) & RHP_HTTP_WIDE)
+        result = *reinterpret_cast<const int32_t *>(p.http + RHP_COMPACT_HTTP_WIDE_OFF(n) + (size_t) i * sizeof(rhp_http_t));
+      else
+        result = (int8_t) (c.x & 0xffu);
+    } else {
+      result = *reinterpret_cast<const int32_t *>(p.http + (size_t) i * sizeof(rhp_http_t));
+    }
+    ready = ready && result == 1;
+  }
+  if (!ready) nh = 0;
+  if (nh > m) nh = m;   /* never more records than the batch holds */
+  const uint64_t at0 = ready ? p.offsets[i] : 0u;   /* the request's first byte */
+
+  /* ---- header lookup ---- */
+  const uint32_t all = (1u << p.n_names) - 1u;
+  uint32_t found = 0;
+  if (p.n_names) {
+    /* rhp_hdr_t records: index i * s_req + k * s_hdr of recs */
+    const uint8_t *recs = p.hdrs;
+    uint64_t s_req = m, s_hdr = 1;
+    if (p.layout == RHP_LAYOUT_HEADER_MAJOR) {
+      s_req = 1;
+      s_hdr = n;
+    }
+    if (lengths) recs = p.hdrs + (dense ? RHP_DENSE_WIDE_OFF(n, m) : RHP_COMPACT_WIDE_OFF(n, m));
+    const bool drm = p.layout == RHP_LAYOUT_DENSE_RM;
+    const uint16_t *lens16 = reinterpret_cast<const uint16_t *>(p.hdrs);
+    const uint32_t *lens32 = reinterpret_cast<const uint32_t *>(p.hdrs);
+    const uint32_t *ovf32 = reinterpret_cast<const uint32_t *>(p.hdrs + RHP_DENSE_OVF_OFF(n, m));
+    uint32_t at = path_off + path_len + 11u;   /* the first header line (rhp.h) */
+    for (uint32_t k = 0; k < nh && found != all; k++) {
+      uint32_t noff, nl, voff, vl;
+      if (!lengths || wide) {
+        const uint2 h = reinterpret_cast<const uint2 *>(recs)[(uint64_t) i * s_req + (uint64_t) k * s_hdr];
+        noff = h.x & 0xffffu;
+        nl = h.x >> 16;
+        voff = h.y & 0xffffu;
+        vl = h.y >> 16;
+        if (noff == RHP_NAME_NULL) continue;   /* name == NULL: an obs-fold line */
+      } else {
+        uint32_t l;
+        if (dense) {
+          const uint64_t idx = drm ? (uint64_t) i * m + k : (uint64_t) k * n + i;
+          l = lens16[idx];
+          l = l == RHP_DENSE_OVERFLOW ? ovf32[idx] : (l & 63u) | (l >> 6) << 16;
+        } else {
+          l = lens32[(uint64_t) k * n + i];
+        }
+        nl = l & 0xffffu;
+        vl = l >> 16;
+        noff = at;
+        voff = (at + nl + 2u) & 0xffffu;
+        at += nl + vl + 4u;
+      }
+      uint32_t cand = nl <= RHP_CLASSIFY_NAME_MAX ? (uint32_t) lenmask[nl] & ~found : 0u;
+      if (cand == 0) continue;
+      if (noff + nl > (uint32_t) ret) continue;   /* (a parsed name lies inside its header section) */
+      cand = same_text<true>(p.bytes + at0 + noff, nl, cand, names, [](uint32_t j) { return j * kNameDwords; });
+      for (uint32_t c = cand; c; c &= c - 1u) p.fields[(uint64_t) __builtin_ctz(c) * n + i] = voff | vl << 16;
+      found |= cand;
+    }
+    for (uint32_t c = all & ~found; c; c &= c - 1u) p.fields[(uint64_t) __builtin_ctz(c) * n + i] = RHP_NAME_NULL;
+  }
+
+  /* ---- route match: lengths first, then the path's and the method's bytes ---- */
+  if (p.route) {
+    uint32_t rt = RHP_ROUTE_NONE;
+    if (ready && p.n_routes) {
+      uint32_t cand = 0, with_method = 0;
+      for (uint32_t r = 0; r < p.n_routes; r++) {
+        const uint32_t ml = r_mlen[r];
+        if (r_tlen[r] == path_len && (ml == 0 || ml == method_len)) cand |= 1u << r;
+        if (ml) with_method |= 1u << r;
+      }
+      if (path_off + path_len > (uint32_t) ret || method_off + method_len > (uint32_t) ret) cand = 0;   /* (as the names) */
+      if (cand) cand = same_text<false>(p.bytes + at0 + path_off, path_len, cand, text, [&](uint32_t r) { return (uint32_t) r_toff[r]; });
+      if (cand & with_method) {
+        const uint32_t ok = same_text<false>(p.bytes + at0 + method_off, method_len, cand & with_method, text,
+                                             [&](uint32_t r) { return (uint32_t) r_moff[r]; });
+        cand = (cand & ~with_method) | ok;
+      }
+      if (cand) rt = (uint32_t) __builtin_ctz(cand);
+    }
+    p.route[i] = (uint16_t) rt;
+  }
+}
+
+/* the caller's tables as the kernel's: names folded, route text packed */
+void pack_tables(const rhp_classify_t *c, CTables &t)
+{
+  memset(&t, 0, sizeof t);
+  for (uint32_t j = 0; j < c->n_names; j++) {
+    const uint8_t *s = c->text + c->names[j].off;
+    const uint32_t len = c->names[j].len;
+    uint8_t *d = reinterpret_cast<uint8_t *>(t.name[j]);
+    for (uint32_t q = 0; q < len; q++) d[q] = s[q] >= 'a' && s[q] <= 'z' ? (uint8_t) (s[q] - 0x20) : s[q];
+    t.name_len[j] = (uint8_t) len;
+  }
+  uint32_t at = 0;   /* dwords of t.text in use */
+  uint8_t *d = reinterpret_cast<uint8_t *>(t.text);
+  for (uint32_t r = 0; r < c->n_routes; r++) {
+    const rhp_span_t sp[2] = {c->routes[r].method, c->routes[r].target};
+    uint16_t off[2];
+    for (int q = 0; q < 2; q++) {
+      off[q] = (uint16_t) at;
+      memcpy(d + 4u * at, c->text + sp[q].off, sp[q].len);
+      at += (sp[q].len + 3u) >> 2;
+    }
+    t.r_moff[r] = off[0];
+    t.r_mlen[r] = (uint16_t) sp[0].len;
+    t.r_toff[r] = off[1];
+    t.r_tlen[r] = (uint16_t) sp[1].len;
+  }
+}
+
+}  // namespace
+
+extern "C" int rhp_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c, void *stream)
+{
+  const int rc = rhp_classify_check(b, c);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  CParams p;
+  pack_tables(c, p.t);
+  p.bytes = b->mode == RHP_MODE_HTTP && b->bytes_rw ? b->bytes_rw : b->bytes;
+  p.offsets = b->offsets;
+  p.reqs = reinterpret_cast<const uint8_t *>(b->reqs);
+  p.hdrs = reinterpret_cast<const uint8_t *>(b->hdrs);
+  p.http = b->mode == RHP_MODE_HTTP ? reinterpret_cast<const uint8_t *>(b->http) : nullptr;
+  p.fields = reinterpret_cast<uint32_t *>(c->fields);
+  p.route = c->route;
+  p.n = b->n;
+  p.m = b->max_headers;
+  p.layout = b->layout;
+  p.n_names = c->n_names;
+  p.n_routes = c->n_routes;
+  hipLaunchKernelGGL(rhp_classify_kernel, dim3((b->n + 255u) / 256u), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
+  return (int) hipGetLastError();
+}

@@ -21,6 +21,7 @@
 #include "rhp_host.h"
 #include "rhp_dfa.h"
 #include "rhp_scalar.h"
+#include "rhp_classify_args.h"
 
 using namespace rhp;
 
@@ -499,6 +500,65 @@ extern "C" int rhp_cpu_pack_dense(const rhp_batch_t *b, rhp_req_dense_t *dreq, r
     dreq[i] = reg ? rhp_req_dense_t{(uint16_t) r.ret, r.path_len, (uint8_t) r.method_len, (uint8_t) r.num_headers,
                                     (uint8_t) r.minor_version, 0}
                   : rhp_req_dense_t{0, 0, 0, 0, 0, (uint8_t) RHP_DENSE_WIDE};
+  }
+  return 0;
+}
+
+/* rhp_classify_batch (rhp.h) on the host, over a parsed batch in host memory:
+ * http_field_lookup (src/reactor/http.c:167-175: the first field whose name is
+ * string_equal_case, src/reactor/data.c:11-28) per name and the first route
+ * whose target and method are string_equal, one request and one byte at a
+ * time over the records as rhp_expand_reqs / rhp_expand_records /
+ * rhp_expand_http give them -- a decode of the layouts that shares nothing
+ * with the kernel's (rhp_classify.hip). */
+extern "C" int rhp_cpu_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c)
+{
+  const int rc = rhp_classify_check(b, c);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const uint32_t n = b->n, m = b->max_headers;
+  const bool http_mode = b->mode == RHP_MODE_HTTP;
+  std::vector<rhp_req_t> reqs(n);
+  std::vector<rhp_hdr_t> hdrs((size_t) n * m);
+  std::vector<rhp_http_t> http(http_mode ? n : 0);
+  if (rhp_expand_reqs(b, b->reqs, reqs.data()) != 0) return -22;
+  if (m && rhp_expand_records(b, reqs.data(), b->hdrs, hdrs.data()) != 0) return -22;
+  if (http_mode && rhp_expand_http(b, reqs.data(), b->http, http.data()) != 0) return -22;
+  const uint8_t *bytes = http_mode && b->bytes_rw ? b->bytes_rw : b->bytes;
+  const auto upper = [](uint8_t x) { return x >= 'a' && x <= 'z' ? (uint8_t) (x - ('a' - 'A')) : x; };   /* C-locale toupper */
+  const auto same = [&](const uint8_t *s, uint32_t len, rhp_span_t t) {
+    return len == t.len && (len == 0 || memcmp(s, c->text + t.off, len) == 0);
+  };
+  for (uint32_t i = 0; i < n; i++) {
+    const rhp_req_t &r = reqs[i];
+    const bool ready = r.ret > 0 && (!http_mode || http[i].result == 1);
+    const uint8_t *req = bytes + b->offsets[i];
+    const uint32_t nh = !ready ? 0u : r.num_headers < m ? r.num_headers : m;
+    for (uint32_t j = 0; j < c->n_names; j++) {
+      const uint8_t *name = c->text + c->names[j].off;
+      const uint32_t len = c->names[j].len;
+      rhp_fieldref_t f = {RHP_NAME_NULL, 0};
+      for (uint32_t k = 0; k < nh; k++) {
+        const rhp_hdr_t &h = hdrs[(size_t) i * m + k];
+        if (h.name_off == RHP_NAME_NULL || h.name_len != len) continue;
+        uint32_t q = 0;
+        while (q < len && upper(req[h.name_off + q]) == upper(name[q])) q++;
+        if (q == len) {
+          f = rhp_fieldref_t{h.value_off, h.value_len};
+          break;
+        }
+      }
+      c->fields[(size_t) j * n + i] = f;
+    }
+    if (!c->route) continue;
+    uint16_t rt = RHP_ROUTE_NONE;
+    for (uint32_t k = 0; ready && k < c->n_routes; k++) {
+      const rhp_route_t &t = c->routes[k];
+      if (same(req + r.path_off, r.path_len, t.target) && (t.method.len == 0 || same(req + r.method_off, r.method_len, t.method))) {
+        rt = (uint16_t) k;
+        break;
+      }
+    }
+    c->route[i] = rt;
   }
   return 0;
 }
