@@ -54,17 +54,9 @@
 #endif
 
 /* bytes of a lane's window per kernel loop iteration: the DFA steps this many
- * bytes between two decodes (kernel and emulator must agree) */
-#ifndef RHP_BLOCK
-#define RHP_BLOCK 64
-#endif
-/* http mode's window extension in 16-byte parts: its windows are RHP_BLOCK +
- * 16 * RHP_HTTP_XPARTS bytes (rhp_kernel.hip, window geometry; measured with 2
- * and not kept) */
-#ifndef RHP_HTTP_XPARTS
-#define RHP_HTTP_XPARTS 0
-#endif
-#define RHP_HTTP_BLOCK (RHP_BLOCK + 16 * RHP_HTTP_XPARTS)
+ * bytes between two decodes.  Not a build option: the kernel's window is a
+ * whole 128-byte HBM line, and the emulator walks the same windows. */
+#define RHP_BLOCK 128
 
 namespace rhp {
 
@@ -362,7 +354,7 @@ static_assert(kRowLayout.bytes != 0, "the lookup rows fit");
 enum : uint32_t {
   kClassRow = kRowLayout.row[0],
   kClassRowR = kRowLayout.row[1],
-  kClassRow16 = kRowLayout.row[2],   /* class(b) * 16: the b0 half of a code (the kernel's code form 2) */
+  kClassRow16 = kRowLayout.row[2],   /* class(b) * 16: the b0 half of a code (not read by the kernel; kept for the layout) */
   kTable2Bytes = kRowLayout.bytes
 };
 RHP_DHD constexpr uint32_t code_row(uint32_t k) { return kRowLayout.row[3 + k]; }   /* k < kClasses */

@@ -25,6 +25,8 @@
 
 using namespace rhp;
 
+static_assert(RHP_BLOCK == 128, "the emulator walks the kernel's 128-byte windows");
+
 namespace {
 
 const Table2 &table()
@@ -175,14 +177,13 @@ extern "C" int rhp_emu_parse_batch(const rhp_batch_t *b, uint64_t *stats /* [3] 
       const uint32_t l = lens16[k * dstride];
       return l == RHP_DENSE_OVERFLOW ? ovf32[k * dstride] : (l & 63u) | (l >> 6) << 16;
     };
-    /* the kernel's window: http mode walks RHP_HTTP_BLOCK bytes per window */
-    const int32_t block = b->mode == RHP_MODE_HTTP ? RHP_HTTP_BLOCK : RHP_BLOCK;
-    constexpr int kMaxWords = (RHP_HTTP_BLOCK > RHP_BLOCK ? RHP_HTTP_BLOCK : RHP_BLOCK) / 32;
-    const int words = block / 32;
+    /* the kernel's window, in both modes */
+    constexpr int32_t block = RHP_BLOCK;
+    constexpr int words = block / 32;
     for (;;) {
       /* one window: steps, then the decode of its event mask (32 bytes per word) */
       const int32_t block_pos = pos;
-      uint32_t evw[kMaxWords];
+      uint32_t evw[words];
       for (int w = 0; w < words; w++) {
         uint32_t ev = 0;
         for (int k = 0; k < 32; k += 2) {   /* one table read per byte pair */

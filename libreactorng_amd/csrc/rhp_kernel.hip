@@ -46,6 +46,19 @@ using namespace rhp;
 
 static_assert(RHP_BLOCK == 128, "the kernel walks 128-byte windows (whole HBM lines)");
 
+/* Geometry a same-box A/B run may sweep (-D...); a build without any -D is the
+ * product.  The third one, RHP_ROW_STRIDE, is in rhp_dfa.h (the table's). */
+/* the occupancy the DFA kernel is compiled for: its register budget is 512 /
+ * RHP_WAVES_PER_SIMD VGPRs per lane (4: 128, one 16-wave workgroup per CU) */
+#ifndef RHP_WAVES_PER_SIMD
+#define RHP_WAVES_PER_SIMD 4
+#endif
+/* waves per workgroup of the phr-mode kernels (16: four per SIMD; 8 and 12
+ * leave LDS and issue slots to fewer waves) */
+#ifndef RHP_PHR_WAVES
+#define RHP_PHR_WAVES 16
+#endif
+
 __device__ const Table2 g_table = make_table2();
 
 struct Params {
@@ -106,14 +119,10 @@ __device__ __forceinline__ void put_http(const Params &p, uint32_t i, const rhp_
   }
 }
 
-#ifndef RHP_WAVES_PER_SIMD
-#define RHP_WAVES_PER_SIMD 4
-#endif
-
 enum : uint32_t {
   kSecDecodeStamp = 6,                           /* Diag section slots of the late form's decode / framing; */
   kSecFrameStamp = 7,                            /* the early form's window reads + [C] / shuffles + [D] */
-  kBlock = 128,                                  /* window bytes per lane per loop iteration (early form) */
+  kBlock = 128,                                  /* window bytes per lane per loop iteration */
   kParts = kBlock / 16,                          /* 16-byte parts per window */
   kEvWords = kBlock / 32,                        /* 32-bit event words per window */
   kLdsTable = (kTable2Bytes + 1023u) & ~1023u,   /* staging starts 1 KiB aligned */
@@ -153,23 +162,13 @@ enum : uint32_t {
 };
 static_assert(idx2(S_DONE, 0) == kPark, "parked lanes sit in DONE");
 
-/* http mode's window extension (16-byte parts past the 128-byte window, see
- * the kernel's window geometry) and the waves its staging leaves room for */
-constexpr uint32_t kHttpXParts = RHP_HTTP_XPARTS;   /* rhp_dfa.h: the emulator walks the same windows */
-constexpr int kHttpWaves = kHttpXParts == 0 ? 16 : kHttpXParts <= 2 ? 12 : 8;
-#ifndef RHP_CODE_FORM
-#define RHP_CODE_FORM 1
-#endif
-constexpr int kCodeForm = RHP_CODE_FORM;   /* how a pair's code is looked up (the walk's look_a / look_b) */
+constexpr int kHttpWaves = 16;   /* waves per workgroup of the http-mode kernels */
 /* the lowest pair index of a state that is not terminal (DONE, ERR, SLOW and
  * their event forms are the indices below it) */
 constexpr uint32_t kLiveIdx = idx2(S_SLOW, 1) + 1u;
 static_assert(idx2(S_DONE, 0) < kLiveIdx && idx2(S_ERR, 1) < kLiveIdx && idx2(S_DONE_E, 3) < kLiveIdx &&
               idx2(S_ERR_E, 3) < kLiveIdx && idx2(S_PRE, 0) >= kLiveIdx && idx2(S_SP1_E, 2) >= kLiveIdx,
               "terminal indices lie below every live one");
-#ifndef RHP_PHASE_LOCK
-#define RHP_PHASE_LOCK 1
-#endif
 
 /* LDS byte address of part q (16 B) of lane w's window inside the staging
  * buffer.  The LDS-DMA loads of a wave write lane-linearly (1 KiB per
@@ -207,8 +206,9 @@ __device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0
  * the replay's start (after the workgroup barrier), 15 / 16 the wave's shader
  * cycles in the replay's pass 2 (listed scalar paths) / pass 1, 17 requests it
  * ran in pass 2, 18 requests it framed in pass 1, 19 the prologue's loads
- * landed, 20 / 21 late form: decode_window / frame_window cycles (inside
- * section 2), 22 / 23 pass 2's validation and serial paths / staged moves.  A section that ends with a wait (`sync`) waits for its LDS reads
+ * landed, 20 / 21 late form: decode_window / framing cycles (inside section
+ * 2), 22 / 23 pass 2's validation and serial paths / staged moves.  A section
+ * that ends with a wait (`sync`) waits for its LDS reads
  * (and, where named, its memory) first, so its cycles include their latency.
  * RHP_CLOCK (diagnostic build, tools/kclock.py): shader ticks and 100 MHz
  * ticks from the entry of block 0 wave 0 to its loop's end. */
@@ -219,6 +219,19 @@ __device__ unsigned long long g_stamps[8192 * kStampSlots];
 #ifdef RHP_CLOCK
 __device__ unsigned long long g_clock[2];
 #endif
+/* Measurement switches (-DRHP_DIAG_...; DESIGN.md "Where the time goes"): each
+ * takes one part of the loop out, or doubles it, so its share of the time
+ * shows; such a build writes wrong records or none and is only ever timed.
+ * RHP_SET(X): X is defined, as nothing or as 1 (an undefined X stringifies to
+ * its own name). */
+#define RHP_SET_(x) (#x[0] == '\0' || #x[0] == '1')
+#define RHP_SET(x) RHP_SET_(x)
+constexpr bool kDiagNoDecode = RHP_SET(RHP_DIAG_NO_DECODE);       /* no decode_window: the decode's share (no records) */
+constexpr bool kDiagNoWalk = RHP_SET(RHP_DIAG_NO_WALK);           /* no walk: its share (every request ends -1 at its last window) */
+constexpr bool kDiagWalkTwice = RHP_SET(RHP_DIAG_WALK_TWICE);     /* early form: each window walked twice, same outputs: a walk's marginal cost */
+constexpr bool kDiagNoRecstore = RHP_SET(RHP_DIAG_NO_RECSTORE);   /* compact records computed, not stored: the stores' share */
+constexpr bool kDiagNoFrame = RHP_SET(RHP_DIAG_NO_FRAME);         /* no in-loop framing (frame_read / frame_eval): its share */
+constexpr bool kDiagNoWt = RHP_SET(RHP_DIAG_NO_WT);               /* plain record stores everywhere: write-through's effect */
 struct Diag {
 #ifdef RHP_STAMPS
   unsigned long long t0 = 0, t1 = 0, c0 = 0, c1 = 0, acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rp[6] = {0, 0, 0, 0, 0, 0};
@@ -391,10 +404,7 @@ struct DevMove {
       partial(A);
       A += 16;
     }
-#ifndef RHP_MOVE_UNROLL
-#define RHP_MOVE_UNROLL 4
-#endif
-    constexpr int U = RHP_MOVE_UNROLL;   /* destination blocks per memory round trip */
+    constexpr int U = 4;   /* destination blocks per memory round trip */
     while (A + 16 * U <= de) {
       const uintptr_t s0 = (A + delta) & ~(uintptr_t) 15;
       u32x4 l[U + 1];
@@ -1088,18 +1098,8 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
 
   const uint32_t maxh = p.max_headers;
   constexpr bool http = HTTP;   /* p.mode == RHP_MODE_HTTP (the launch picks the instance) */
-  /* Window geometry.  Windows are 128 bytes (whole HBM lines).  The http form
-   * can walk kHttpXParts 16-byte parts more (RHP_HTTP_XPARTS, rhp_dfa.h), so a
-   * header section that fits (config 5: 133 B) is walked, decoded and framed in
-   * one iteration where 128 B takes two; the extension parts go to a staging
-   * area of their own (xstage: part 8 + k of every lane's window at 1024 k +
-   * 16 lane), fetched by kXParts more LDS-DMA loads per issue, and the
-   * staging leaves room for 12 waves.  Measured with 2 parts (160 B,
-   * profiles/r04/e/): config 5 +2-4 % (the fewer waves cost more than the
-   * iterations saved) and no fewer bytes fetched (the 32 B of the next line
-   * cost its whole line), so the default is 0. */
-  constexpr uint32_t kXParts = (LATE && HTTP) ? kHttpXParts : 0u;
-  /* Phase lock (http form, RHP_PHASE_LOCK): a lane walks the first window of a
+  /* Windows are kBlock = 128 bytes (whole HBM lines) in every form.
+   * Phase lock (http form): a lane walks the first window of a
    * request only on even iterations.  Header sections of one or two windows
    * (config 5: 133 B) then keep every lane of a wave in step -- first windows on
    * even iterations, second windows on odd ones -- and on an odd iteration
@@ -1107,12 +1107,8 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
    * walk stops (walk()).  A lane whose request ended in its first window idles
    * one iteration; without the lock the lanes drift out of step after the
    * first such request and no walk ever stops early. */
-  constexpr bool kPhaseLock = RHP_PHASE_LOCK && LATE && HTTP;
+  constexpr bool kPhaseLock = LATE && HTTP;
   uint32_t it_odd = 0;   /* wave-uniform: this iteration's number is odd */
-  constexpr uint32_t kWParts = kParts + kXParts;   /* 16-byte parts per window */
-  constexpr uint32_t kWBlock = 16u * kWParts;      /* window bytes */
-  constexpr uint32_t kWEv = kWBlock / 32u;         /* 32-bit event words per window */
-  static_assert(kWBlock % 32u == 0, "whole event words per window");
 
   /* ---- request pool ----
    * Workgroup g owns requests [g*span, (g+1)*span) (host: span = n / grid).
@@ -1158,7 +1154,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
    * the emulator mirrors, does not depend on the buffer's address) and no line
    * is fetched by two windows of one request.  http mode fetches from the dword
    * holding it (kLead = 3): its requests are framed from the window (the GET
-   * check, frame_window) at positions the 4-byte alignment keeps in the first
+   * check, frame_read) at positions the 4-byte alignment keeps in the first
    * part. */
   constexpr uint32_t kLead = HTTP ? 3u : 127u;
   const uint64_t base = o_lo & ~(uint64_t) kLead;
@@ -1185,25 +1181,20 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
   uint32_t wcur = 0, wlen = 0, wget = 0, cur_ptr = 0;
   uint32_t wlead = 0;                  /* bytes before wcur in its first window (wnew) */
   uint32_t woff = 0;                   /* wcur's first byte, offset from base (LATE http framing) */
-  uint32_t ev[kWEv];                   /* events of the window being walked (32 bytes per word) */
+  uint32_t ev[kEvWords];                   /* events of the window being walked (32 bytes per word) */
   bool pend_ok = false;                /* pend: the lane's next request */
   uint32_t pend = 0;
   uint32_t pend_o0 = 0, pend_o1 = 0;   /* low dwords of offsets[pend], offsets[pend+1] as loaded */
   uint32_t nw = 0;                     /* next window: byte offset from base | kind (0 none, 1
                                           continuation, 2 first window of pend); windows are 4-aligned */
-  u32x4 W[kWParts];                    /* the window in registers */
+  u32x4 W[kParts];                    /* the window in registers */
   const uint32_t stage = __builtin_amdgcn_readfirstlane(kLdsTable + (tid >> 6) * kStageWave);   /* wave-uniform */
-  /* the extension parts of the wave's windows (kXParts > 0): after the pool area */
-  const uint32_t xstage = __builtin_amdgcn_readfirstlane(kLdsTable + WAVES * kStageWave + kPoolBytes + 4u * kOrderBuckets +
-                                                         (tid >> 6) * 1024u * kXParts);
   /* the first window of the request starting at (low dword) o0, offset from
    * base, and the number of bytes before the request in it (see kLead) */
   auto first_win = [&](uint32_t o0) -> uint32_t { return (o0 - (uint32_t) base) & ~kLead; };
   auto lead_of = [&](uint32_t o0) -> uint32_t { return (o0 - (uint32_t) base) & kLead; };
   /* LDS address of part q of this lane's window */
-  auto part_lds = [&](uint32_t q) -> uint32_t {
-    return q < kParts ? stage + stage_off(lane, q) : xstage + 1024u * (q - kParts) + 16u * lane;
-  };
+  auto part_lds = [&](uint32_t q) -> uint32_t { return stage + stage_off(lane, q); };
 
   /* ---- decode state (the request whose previous window is decoded) ----
    *   kn   request-line events consumed (0 ME, 1 PE, 2 RL, 3 done) | minor << 3
@@ -1218,7 +1209,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
   bool dhas = false;
   uint32_t dcur = 0, dlen = 0, st_prev = kPark, doff = 0;
   int32_t dpos = 0;                    /* position of the decoded window's first byte */
-  uint32_t evp[kWEv];                  /* its events */
+  uint32_t evp[kEvWords];                  /* its events */
   uint32_t kn = 0, me = 0, pe = 0, rl = 0, nh = 0, ls = 0, t = 0, pco = 0, ovf = 0;
   uint32_t cand = 0, crec_lo = 0, crec_hi = 0;
   /* http framing in the late-issue kernel (http.c:196-218), from the
@@ -1230,7 +1221,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
   uint32_t fr = 0;
   uint64_t fv = 0;
 #pragma unroll
-  for (int w = 0; w < (int) kWEv; w++) ev[w] = evp[w] = 0;
+  for (int w = 0; w < (int) kEvWords; w++) ev[w] = evp[w] = 0;
 
   /* give every lane without a pending request one from the pool; the offsets
    * loads are only consumed at the top of the next block */
@@ -1332,7 +1323,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
    * exceeds maxh and every completed record is stored.  Updates are written as
    * arithmetic on the conditions (m & (m - c), x + c * d) so the compiler emits
    * straight-line code, not exec-masked branches. */
-  uint32_t mq[kWEv];
+  uint32_t mq[kEvWords];
   uint32_t term_pos = 0xffffffffu, dstop = 0;
   /* hx: index in hdrs of the decoded request's next header record (set per
    * window from dcur and nh, not carried across the walk; the host keeps
@@ -1370,7 +1361,6 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
        * lanes with a record in the word loop over their records under exec
        * (a lane leaves the loop after its last record), one record per trip;
        * the store flavour is chosen outside the loop */
-#ifndef RHP_DECODE_SELECT
       if (eolm != 0) {
         auto records = [&](auto wt_c) __attribute__((always_inline)) {
           do {
@@ -1389,13 +1379,10 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
               if (!fits) *GLOBAL(uint32_t, p.ovf32 + hx) = nlen | vlen << 16;   /* rare: the overflow area */
             } else if constexpr (COMPACT) {
               uint32_t *q = p.lens + hx;
-#ifdef RHP_DIAG_NO_RECSTORE   /* diagnostic: the records computed, not stored (the stores' share) */
-              asm volatile("" ::"v"(q), "v"(nlen | vlen << 16));
-#else
-              if constexpr (decltype(wt_c)::value)
+              if constexpr (kDiagNoRecstore) asm volatile("" ::"v"(q), "v"(nlen | vlen << 16));
+              else if constexpr (decltype(wt_c)::value)
                 asm volatile("global_store_dword %0, %1, off sc1" ::"v"(q), "v"(nlen | vlen << 16) : "memory");
               else *GLOBAL(uint32_t, q) = nlen | vlen << 16;
-#endif
             } else {
               rhp_hdr_t *q = p.hdrs + hx;
               const u32x2 v = u32x2{ls | nlen << 16, (co + 2u) | vlen << 16};
@@ -1419,33 +1406,6 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
         if (wt) records(std::true_type{});
         else records(std::false_type{});
       }
-#else
-      /* Straight-line body for every lane: a lane whose word is done (eolm ==
-       * 0) computes a dead record, stores nothing and keeps its state */
-      while (uint64_t st_m = __builtin_amdgcn_ballot_w64(eolm != 0)) {
-        const bool has = eolm != 0;
-        const uint32_t e = base + (uint32_t) __builtin_ctz(eolm | 0x80000000u);
-        const uint32_t co = t ? pco : base + (uint32_t) __builtin_ctz(com | 0x80000000u);
-        const uint32_t lo = ls | ((co - ls) << 16), hi = (co + 2u) | ((e - co - 3u) << 16);
-        if constexpr (DENSE) store_dense_lanes(st_m, p, hx, co - ls, e - co - 3u, wt);
-        else if constexpr (COMPACT) store_len_lanes(st_m, p.lens + hx, (co - ls) | ((e - co - 3u) << 16), wt);
-        else store_rec_lanes(st_m, p.hdrs + hx, u32x2{lo, hi}, wt);
-        if (http) {   /* uniform: framing candidates only in http mode */
-          const uint32_t nlen = co - ls;
-          const bool cnd = has && (nlen == 14u || nlen == 17u);
-          const bool first = cnd && (cand & 0xbfffffffu) == 0;
-          crec_lo = first ? lo : crec_lo;
-          crec_hi = first ? hi : crec_hi;
-          cand |= cnd ? (nh < 30u ? 1u << nh : 0x80000000u) : 0u;
-        }
-        com &= com - (uint32_t) (has && !t);
-        eolm &= eolm - 1u;
-        ls = has ? e + 1u : ls;
-        nh += (uint32_t) has;
-        hx += has ? p.rec_hdr : 0u;
-        t = has ? 0u : t;
-      }
-#endif
       /* a colon left open at the end of the word: a later word (or window) has its LF */
       if (com) {
         pco = base + (uint32_t) __builtin_ctz(com);
@@ -1493,7 +1453,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
   };
   auto decode_window = [&]() {
 #pragma unroll
-    for (int q = 0; q < (int) kWEv; q++) word(mq[q], (uint32_t) dpos + 32u * (uint32_t) q);
+    for (int q = 0; q < (int) kEvWords; q++) word(mq[q], (uint32_t) dpos + 32u * (uint32_t) q);
   };
   /* The framing candidate's evaluation after a window's decode (see fr).  A
    * lane that needs bytes reads the 36 bytes from one position r of the
@@ -1511,7 +1471,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     uint32_t raw[10];
   };
   auto frame_read = [&](FrameIn &fi, uint32_t crec_before) __attribute__((always_inline)) {
-    const uint32_t wend = (uint32_t) dpos + kWBlock;
+    const uint32_t wend = (uint32_t) dpos + kBlock;
     const uint32_t hdr = cand & 0x3fffffffu;
     const bool rec_done = (crec_lo | (cand & 0xbfffffffu)) != crec_before && hdr != 0 && (hdr & (hdr - 1u)) == 0 &&
                           !(cand >> 31);
@@ -1561,7 +1521,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     for (uint32_t k = 0; k < 10; k++) {   /* bytes past the window wrap inside the lane's window: never used */
       const uint32_t b = b0 + 4u * k;
       fi.raw[k] = *reinterpret_cast<const __attribute__((address_space(3))) uint32_t *>(
-          (size_t) (part_lds((b >> 4) % kWParts) + (b & 15u)));
+          (size_t) (part_lds((b >> 4) % kParts) + (b & 15u)));
     }
   };
   auto frame_eval = [&](FrameIn &fi) __attribute__((always_inline)) {
@@ -1638,11 +1598,6 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
       if ((n > 12u && !(fr & kFrStop)) || ((fr >> kFrCountSh) & 0xffu) > kFrMaxValue) fr |= kFrDefer;
     }
   };
-  auto frame_window = [&](uint32_t crec_before) __attribute__((always_inline)) {
-    FrameIn fi;
-    frame_read(fi, crec_before);
-    frame_eval(fi);
-  };
   /* set up the decode of the window walked last iteration */
   auto decode_begin = [&]() {
     const uint32_t e = st_prev;
@@ -1650,7 +1605,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     const bool term_ev = is_done2(e) || is_err2(e);
     const uint32_t live = (slow || !dhas || ovf) ? 0u : 0xffffffffu;
 #pragma unroll
-    for (int q = 0; q < (int) kWEv; q++) mq[q] = evp[q] & live;
+    for (int q = 0; q < (int) kEvWords; q++) mq[q] = evp[q] & live;
     term_pos = 0xffffffffu;
     dstop = 0;
     hx = dcur * p.rec_req + nh * p.rec_hdr;
@@ -1659,7 +1614,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
       int q = 0;
       uint32_t w = mq[0];
 #pragma unroll
-      for (int k = 1; k < (int) kWEv; k++) {
+      for (int k = 1; k < (int) kEvWords; k++) {
         q = mq[k] ? k : q;
         w = mq[k] ? mq[k] : w;
       }
@@ -1667,7 +1622,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
       if (w) term_pos = (uint32_t) dpos + 32u * (uint32_t) q + bt;
       w &= ~(1u << bt);
 #pragma unroll
-      for (int k = 0; k < (int) kWEv; k++) mq[k] = k == q ? w : mq[k];
+      for (int k = 0; k < (int) kEvWords; k++) mq[k] = k == q ? w : mq[k];
     }
   };
   /*
@@ -1681,7 +1636,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     const uint32_t e = st_prev;
     const bool ovfl = ovf != 0;
     const bool term_ev = is_done2(e) || is_err2(e);
-    const bool fin = dhas && (ovfl || is_slow2(e) || term_ev || (uint32_t) dpos + kWBlock >= dlen);
+    const bool fin = dhas && (ovfl || is_slow2(e) || term_ev || (uint32_t) dpos + kBlock >= dlen);
     if (!fin) return false;
     bool ok = !ovfl && is_done2(e) && term_pos < dlen && term_pos < RHP_MAX_LEN;
     /* an ERR between the path and the request-line end (the version, kn == 2)
@@ -1689,10 +1644,10 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
      * len >= PE + 10 */
     bool bad = ovfl ? ovf - 1u < dlen
                     : (is_err2(e) && term_pos < dlen && ((kn & 7u) != 2u || pe + 10u <= dlen));
-#ifdef RHP_DIAG_NO_WALK
-    ok = false;   /* diagnostic: nothing was walked; every request ends at its last window, -1, no replay */
-    bad = true;
-#endif
+    if constexpr (kDiagNoWalk) {   /* nothing was walked: no replay either */
+      ok = false;
+      bad = true;
+    }
     if (!http && p.last_len) {
       /* last_len != 0 (rare: a batch that carries it): is_complete runs first
        * (picohttpparser.c:399-401).  Scanning from last_len - 3 at or before
@@ -1745,7 +1700,6 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
         }
         if (!framed) {
           defer(dcur);
-          typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
           bool chunked = false;
           if constexpr (LATE) {
             const uint32_t hdr = cand & 0x3fffffffu;
@@ -1765,7 +1719,6 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
       rq[3] = (uint32_t) kDeferExact << 16;   /* exact path: replay */
       defer(dcur);
       if (http) {
-        typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
         *GLOBAL(u32x4a4, &p.http[dcur]) = u32x4a4{0u, kHintExact, 0u, 0u};
       }
     }
@@ -1785,29 +1738,25 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     return true;
   };
 
-  /* Pair codes by two lookups.  Form 1 (rhp_dfa.h code_row): A = the row of
-   * class(b1), B = class(b0) * 16 + class(b1) from that row: the code read's
-   * address is one v_perm, but lanes whose b0 share an LDS bank and whose b1
-   * differ in class read different rows there (a bank conflict: 3.25 LDS cycles
-   * per read on config 2 where 2 is conflict free, tools/lds_conflicts.py).
-   * Form 2 (RHP_CODE_FORM=2): A = class(b1), B = class(b0) * 16, each from one
-   * 256-byte row (conflict free for bytes < 0x80), code = A | B: one more
-   * v_or per pair.  The table sits at LDS address 0, so a v_perm result is the
-   * address itself. */
+  /* Pair codes by two lookups (rhp_dfa.h code_row): A = the row of class(b1),
+   * B = class(b0) * 16 + class(b1) from that row: the code read's address is
+   * one v_perm, but lanes whose b0 share an LDS bank and whose b1 differ in
+   * class read different rows there (a bank conflict: 3.25 LDS cycles per read
+   * on config 2 where 2 is conflict free, tools/lds_conflicts.py).  The table
+   * sits at LDS address 0, so a v_perm result is the address itself. */
   auto look_a = [&](uint32_t dw, int j) -> uint32_t {
-    return lds_u8(__builtin_amdgcn_perm(kCodeForm == 2 ? kClassRow : kClassRowR, dw, 0x0c0c0400u | (uint32_t) (2 * (j & 1) + 1)));
+    return lds_u8(__builtin_amdgcn_perm(kClassRowR, dw, 0x0c0c0400u | (uint32_t) (2 * (j & 1) + 1)));
   };
   auto look_b = [&](uint32_t a, uint32_t dw, int j) -> uint32_t {
-    return lds_u8(__builtin_amdgcn_perm(kCodeForm == 2 ? kClassRow16 : a, dw, 0x0c0c0400u | (uint32_t) (2 * (j & 1))));
+    return lds_u8(__builtin_amdgcn_perm(a, dw, 0x0c0c0400u | (uint32_t) (2 * (j & 1))));
   };
-  auto code_of = [&](uint32_t a, uint32_t b) -> uint32_t { return kCodeForm == 2 ? (a | b) : b; };
   auto codes_a = [&](const u32x4 &chunk, uint32_t (&r)[8]) {
 #pragma unroll
     for (int j = 0; j < 8; j++) r[j] = look_a(chunk[j >> 1], j);
   };
   auto codes_b = [&](const u32x4 &chunk, const uint32_t (&r)[8], uint32_t (&c)[8]) {
 #pragma unroll
-    for (int j = 0; j < 8; j++) c[j] = code_of(r[j], look_b(r[j], chunk[j >> 1], j));
+    for (int j = 0; j < 8; j++) c[j] = look_b(r[j], chunk[j >> 1], j);
   };
   /* The walk of the window in W: part 0's codes first, then per chained step
    * one independent lookup pair for the next part behind the step's read (its
@@ -1817,14 +1766,11 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
    * fourth step: config 2 +3 %). */
   auto walk = [&]() {
     uint32_t c[8], r[8];
-#if defined(RHP_DIAG_EXTRA_LDS) || defined(RHP_DIAG_EXTRA_VALU)
-    uint32_t xacc = 0;   /* diagnostic: one more LDS read / three more VALU per pair (the walk's sensitivity) */
-#endif
     codes_a(W[0], r);
     codes_b(W[0], r, c);
 #pragma unroll
-    for (int q = 0; q < (int) kWParts; q++) {
-      const bool nx = q + 1 < (int) kWParts;
+    for (int q = 0; q < (int) kParts; q++) {
+      const bool nx = q + 1 < (int) kParts;
       uint32_t cn[8];
 #pragma unroll
       for (int j = 0; j < 8; j++) {
@@ -1832,18 +1778,6 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
         __builtin_amdgcn_sched_barrier(0);   /* the chained read issues first */
         if (nx) r[j] = look_a(W[q + 1][j >> 1], j);
         if (nx && j > 0) cn[j - 1] = look_b(r[j - 1], W[q + 1][(j - 1) >> 1], j - 1);
-#ifdef RHP_DIAG_EXTRA_LDS
-        if (nx) xacc += lds_u8(__builtin_amdgcn_perm(kClassRow, W[q + 1][j >> 1], 0x0c0c0400u | (uint32_t) (2 * (j & 1))));
-#endif
-#ifdef RHP_DIAG_EXTRA_VALU
-        if (nx) {
-          uint32_t y = __builtin_amdgcn_perm(W[q + 1][j >> 1], W[q + 1][j >> 1], 0x0c0c0001u + 0x202u * (uint32_t) (j & 1));
-          opaque(y);
-          y = y ^ ((y >> 6) & 0x7cu);
-          opaque(y);
-          xacc += y;
-        }
-#endif
         __builtin_amdgcn_sched_barrier(0);
         ev_shift2(ev[q >> 1], st);
         __builtin_amdgcn_sched_barrier(0);
@@ -1851,7 +1785,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
       if (nx) {
         cn[7] = look_b(r[7], W[q + 1][3], 7);
 #pragma unroll
-        for (int j = 0; j < 8; j++) c[j] = code_of(r[j], cn[j]);
+        for (int j = 0; j < 8; j++) c[j] = cn[j];
       }
       /* phase-locked http form: once every lane of the wave is terminal (or
        * parked) the rest of the window changes nothing -- terminal states are
@@ -1860,9 +1794,6 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
       if constexpr (kPhaseLock)
         if ((q & 1) && nx && !__builtin_amdgcn_ballot_w64(st >= kLiveIdx)) break;
     }
-#if defined(RHP_DIAG_EXTRA_LDS) || defined(RHP_DIAG_EXTRA_VALU)
-    asm volatile("" ::"v"(xacc));
-#endif
   };
 
   /* The bytes of a first window before its request (wlead of them) zeroed in
@@ -1871,7 +1802,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     if (!__builtin_amdgcn_ballot_w64(wnew && wlead != 0)) return;
     const int32_t l8 = wnew ? (int32_t) (8u * wlead) : 0;
 #pragma unroll
-    for (uint32_t q = 0; q < kLead / 16u + 1u && q < kWParts; q++)
+    for (uint32_t q = 0; q < kLead / 16u + 1u && q < kParts; q++)
 #pragma unroll
       for (uint32_t d = 0; d < 4u; d++) {
         /* the dword's bytes before the request: a v_sub, a v_med3, a 64-bit shift, a v_and */
@@ -1906,11 +1837,7 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
      * straddle lines share their edge lines with the neighbouring requests'
      * windows, which then hit in L2 (non-temporal: config 3 -5 %) */
     const bool aligned = !(nw & 3u) || ((uint32_t) (uintptr_t) (wbytes + src) & (kBlock - 1u)) == 0;
-#ifdef RHP_NO_NT
-    const bool nt = false && aligned;
-#else
     const bool nt = !__builtin_amdgcn_ballot_w64(!aligned);
-#endif
     /* one branch per issue, not one per load (the cache policy is an immediate) */
 #define RHP_ISSUE_LOADS(AUX)                                                                             \
     _Pragma("unroll") for (int i = 0; i < (int) kParts; i++) {                                           \
@@ -1921,11 +1848,6 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     }
     if (nt) { RHP_ISSUE_LOADS(2) } else { RHP_ISSUE_LOADS(0) }
 #undef RHP_ISSUE_LOADS
-    /* the extension parts: lane j's own window, part 8 + k at xstage + 1024 k + 16 j */
-#pragma unroll
-    for (uint32_t k = 0; k < kXParts; k++)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (__attribute__((address_space(3))) void *) (lds + xstage + 1024u * k),
-                                               16, src + kBlock + 16u * k, 0, 0, 0);
   };
   auto issue = [&]() {
     Issue is;
@@ -1957,24 +1879,17 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
   dg.loads_landed();
   const bool uneven =
       may_order && __builtin_amdgcn_ballot_w64((uint64_t) (s1 - s0) * span_n > 2u * (o_hi - o_lo)) != 0;
-  wt = p.wt_records && !uneven;
-#ifdef RHP_DIAG_NO_WT   /* diagnostic: plain record stores everywhere */
-  wt = false;
-#endif
+  wt = !kDiagNoWt && p.wt_records && !uneven;
   /* An uneven range runs on 15 of the 16 waves (14 when its order needs two
    * waves' staging; the others hold the hand-out order and only join the
    * barriers and the replay).
    * Round 3, traffic-bound with 4-aligned windows: 16 waves 422 us, 12 waves 398
    * us, 8 waves 474 us; round 5, after line windows the loop is latency-bound and
    * more waves pay again: 12 waves 282 us, 13: 278, 14: 277 (profiles/r05/config3/). */
-#ifndef RHP_UNEVEN_WAVES
-#define RHP_UNEVEN_WAVES 15
-#endif
   /* the order lives in the last order_waves waves' staging (sort_range): they
-   * must not walk, so at least one wave stays idle whatever the knobs (the http
-   * instance has fewer waves with RHP_HTTP_XPARTS > 0) */
-  constexpr uint32_t kUnevenWaves = (uint32_t) WAVES - 1u < (uint32_t) RHP_UNEVEN_WAVES ? (uint32_t) WAVES - 1u
-                                                                                     : (uint32_t) RHP_UNEVEN_WAVES;
+   * must not walk, so at least one wave stays idle however few waves the
+   * workgroup has (RHP_PHR_WAVES) */
+  constexpr uint32_t kUnevenWaves = (uint32_t) WAVES - 1u < 15u ? (uint32_t) WAVES - 1u : 15u;
   static_assert(kUnevenWaves + 1u <= (uint32_t) WAVES, "an idle wave's staging holds the hand-out order");
   bool idle_wave = false;
   if (uneven) {
@@ -2020,26 +1935,8 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
    * dispatched last in a workgroup run slowest and finish its range last.
    * Rotating every wave's priority each iteration (phase by wave) shares the
    * issue slots evenly (config 2 -1 %, configs 3 and 5 -3 %). */
-#ifndef RHP_PRIO_PHASE_SHIFT
-#define RHP_PRIO_PHASE_SHIFT 6
-#endif
-#ifndef RHP_PRIO_MODE
-#define RHP_PRIO_MODE 0
-#endif
-  uint32_t prio_it = (tid >> RHP_PRIO_PHASE_SHIFT) & 3u;
-#if RHP_PRIO_MODE == 1
-  /* static, graded by dispatch order: the younger a wave on its SIMD, the higher */
-  switch ((tid >> 8) & 3u) {
-  case 0: __builtin_amdgcn_s_setprio(0); break;
-  case 1: __builtin_amdgcn_s_setprio(1); break;
-  case 2: __builtin_amdgcn_s_setprio(2); break;
-  default: __builtin_amdgcn_s_setprio(3);
-  }
-#elif RHP_PRIO_MODE == 2
-  if ((tid >> 9) & 1u) __builtin_amdgcn_s_setprio(1);   /* static: the younger half of the workgroup */
-#endif
+  uint32_t prio_it = (tid >> 6) & 3u;
   while (!idle_wave) {
-#if RHP_PRIO_MODE == 0
     prio_it = (prio_it + 1u) & 3u;
     switch (prio_it) {
     case 0: __builtin_amdgcn_s_setprio(0); break;
@@ -2047,18 +1944,13 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     case 2: __builtin_amdgcn_s_setprio(2); break;
     default: __builtin_amdgcn_s_setprio(3);
     }
-#elif RHP_PRIO_MODE == 3
-    /* the gap between the window's landing and the next window's issue at the
-     * top priority; the rest of the iteration rotates among 0-2 (below) */
-    __builtin_amdgcn_s_setprio(3);
-#endif
     dg.mark();
     /* [A] */
     wait_vm0();   /* the window's LDS-DMA has landed (and the pending offsets, and older stores) */
     dg.section(0);
     const uint32_t p_o0 = pend_o0, p_o1 = pend_o1;
 #pragma unroll
-    for (int q = 0; q < (int) kWParts; q++) W[q] = *reinterpret_cast<const u32x4 *>(lds + part_lds((uint32_t) q));
+    for (int q = 0; q < (int) kParts; q++) W[q] = *reinterpret_cast<const u32x4 *>(lds + part_lds((uint32_t) q));
     /* [C] */
     const uint32_t nw_kind = nw & 3u;
     bool wnew = false;
@@ -2095,25 +1987,15 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
       /* [E] next window: continuation of wcur, else the first window of a ready
        * pend (its addresses exchanged now, the loads made after [D]) */
       nw = 0;
-      if (walking && (uint32_t) (wpos + (int32_t) kWBlock) < wlen) nw = (cur_ptr + kWBlock) | 1u;
+      if (walking && (uint32_t) (wpos + (int32_t) kBlock) < wlen) nw = (cur_ptr + kBlock) | 1u;
       else if (pend_ready) nw = first_win(p_o0) | 2u;
       issue_prep(is);
-#ifndef RHP_REFILL_FIRST
       /* the loads first, [D]'s refill (an LDS atomic round trip and the pending
        * offsets' loads) after them: from the window's landing to the next
        * window's issue a wave has nothing of its own in flight */
       dg.section(kSecFrameStamp, true);   /* stamps: the shuffles */
       wait_lgkm0();   /* [A]'s reads of the buffer and the shuffles are done */
       issue_go(is);
-#endif
-#if RHP_PRIO_MODE == 3
-      prio_it = prio_it == 2u ? 0u : prio_it + 1u;
-      switch (prio_it) {
-      case 0: __builtin_amdgcn_s_setprio(0); break;
-      case 1: __builtin_amdgcn_s_setprio(1); break;
-      default: __builtin_amdgcn_s_setprio(2);
-      }
-#endif
     }
     /* [D] */
     refill_pend();
@@ -2121,35 +2003,24 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     const bool any_dec = __builtin_amdgcn_ballot_w64(dhas) != 0;
     dg.lanes(walking, pool_dry);
     if constexpr (!LATE) {
-#ifdef RHP_REFILL_FIRST
-      dg.section(kSecFrameStamp, true);   /* stamps: the shuffles and [D]'s refill */
-      wait_lgkm0();   /* [A]'s reads of the buffer and the shuffles are done */
-      issue_go(is);
-#endif
       dg.section(1, true);
       /* [F] walk + decode of the previous window */
       decode_begin();
-#ifndef RHP_DIAG_NO_DECODE   /* diagnostic builds only (records not written): the decode's share of the loop */
-      if (any_dec) decode_window();
-#endif
+      if (!kDiagNoDecode && any_dec) decode_window();
 #pragma unroll
-      for (int w = 0; w < (int) kWEv; w++) ev[w] = 0;
+      for (int w = 0; w < (int) kEvWords; w++) ev[w] = 0;
       dg.section(2, true, true);
       if (any_walk) {
         if (!walking) st = kPark;   /* idle lanes step in the parked terminal state */
         zero_lead(wnew);
-#ifndef RHP_DIAG_NO_WALK   /* diagnostic builds only (every request then ends at its buffer's end): the walk's share */
-#ifdef RHP_DIAG_WALK_TWICE   /* diagnostic: the window walked twice from the same state (same outputs): a walk's marginal cost */
-        {
+        if constexpr (kDiagWalkTwice && !kDiagNoWalk) {   /* the first of the two walks, its outputs dropped */
           uint32_t st0 = st;
           opaque(st0);
           walk();
           opaque(st);
           st = st0;
         }
-#endif
-        walk();
-#endif
+        if constexpr (!kDiagNoWalk) walk();
       }
     } else {
       /* [F] walk, then decode the walked window at once (not one behind): a
@@ -2162,13 +2033,11 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
       (void) any_dec;
       dg.section(1);
 #pragma unroll
-      for (int w = 0; w < (int) kWEv; w++) ev[w] = 0;
+      for (int w = 0; w < (int) kEvWords; w++) ev[w] = 0;
       if (any_walk) {
         if (!walking) st = kPark;
         zero_lead(wnew);
-#ifndef RHP_DIAG_NO_WALK   /* diagnostic builds only (see the early form) */
-        walk();
-#endif
+        if constexpr (!kDiagNoWalk) walk();
       }
       dg.section(3, true);
       if (walking && wnew) {
@@ -2185,61 +2054,34 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
       dpos = wpos;
       st_prev = st;
 #pragma unroll
-      for (int w = 0; w < (int) kWEv; w++) evp[w] = ev[w];
+      for (int w = 0; w < (int) kEvWords; w++) evp[w] = ev[w];
       decode_begin();
       const uint32_t crec_before = crec_lo | (cand & 0xbfffffffu);
-#ifndef RHP_DIAG_NO_DECODE   /* diagnostic builds only (see the early form) */
-      if (any_walk) decode_window();
-#endif
+      if (!kDiagNoDecode && any_walk) decode_window();
       dg.section(kSecDecodeStamp, true);
-#ifndef RHP_FRAME_JOINED
       /* the framing's reads of the staging buffer, the next window's issue,
        * then the framing's evaluation and the finalize (which the issue does
        * not wait for: a walk ends at a terminal, its last byte or a max_headers
        * stop, all known after the decode): the window has the evaluation and
        * the finalize to land in (config 5 78.4 -> 75.1 us same-box,
-       * profiles/r06/ab/ab_r6m_post.txt; RHP_FRAME_JOINED: the issue after
-       * the finalize, as before) */
+       * profiles/r06/ab/ab_r6m_post.txt) */
       FrameIn fi;
       fi.need = false;
-#ifndef RHP_DIAG_NO_FRAME
-      if (http && any_walk) frame_read(fi, crec_before);
-#endif
+      if (!kDiagNoFrame && http && any_walk) frame_read(fi, crec_before);
       if (walking && (ovf != 0 || is_done2(st) || is_err2(st) || is_slow2(st) ||
-                      (uint32_t) (wpos + (int32_t) kWBlock) >= wlen))
+                      (uint32_t) (wpos + (int32_t) kBlock) >= wlen))
         wact = false;
       nw = 0;
-      if (walking && wact) nw = (cur_ptr + kWBlock) | 1u;
+      if (walking && wact) nw = (cur_ptr + kBlock) | 1u;
       else if (pend_ok && (!kPhaseLock || it_odd)) nw = first_win(pend_o0) | 2u;   /* the next iteration is even */
       Issue is;
       issue_prep(is);   /* the address shuffles go out with the framing's reads */
       wait_lgkm0();     /* the framing's reads of the buffer are done */
       issue_go(is);
-#ifndef RHP_DIAG_NO_FRAME
-      if (http && any_walk) frame_eval(fi);
-#endif
+      if (!kDiagNoFrame && http && any_walk) frame_eval(fi);
       dg.section(kSecFrameStamp, true);
       if (any_walk) (void) decode_end();
       dg.section(2, true);
-#else
-#ifndef RHP_DIAG_NO_FRAME   /* diagnostic builds only: the in-loop framing's share */
-      if (http && any_walk) frame_window(crec_before);
-#endif
-      dg.section(kSecFrameStamp, true);
-      const bool done = any_walk ? decode_end() : false;
-      dg.section(2, true);
-      /* the walk of wcur ends with this window: finalized (a terminal, a
-       * max_headers stop), or its last byte */
-      if (walking && (done || is_done2(st) || is_err2(st) || is_slow2(st) ||
-                      (uint32_t) (wpos + (int32_t) kWBlock) >= wlen))
-        wact = false;
-      /* [E] (the decode above read the staging buffer the issue refills) */
-      nw = 0;
-      if (walking && wact) nw = (cur_ptr + kWBlock) | 1u;
-      else if (pend_ok && (!kPhaseLock || it_odd)) nw = first_win(pend_o0) | 2u;   /* the next iteration is even */
-      wait_lgkm0();   /* the decode's reads of the buffer are done */
-      issue();
-#endif
     }
     dg.section(LATE ? 4 : 3, true);
     /* [G] */
@@ -2260,14 +2102,14 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
       dpos = wpos;
       st_prev = st;
 #pragma unroll
-      for (int w = 0; w < (int) kWEv; w++) evp[w] = ev[w];
+      for (int w = 0; w < (int) kEvWords; w++) evp[w] = ev[w];
       /* the walk of wcur ends with this window: a terminal, or its last byte */
-      if (is_done2(st) || is_err2(st) || is_slow2(st) || (uint32_t) (wpos + (int32_t) kWBlock) >= wlen) wact = false;
+      if (is_done2(st) || is_err2(st) || is_slow2(st) || (uint32_t) (wpos + (int32_t) kBlock) >= wlen) wact = false;
     } else {
       dhas = false;
     }
     }
-    wpos += (int32_t) kWBlock;
+    wpos += (int32_t) kBlock;
     it_odd ^= 1u;
     dg.iteration_end();
     if (!__ballot(dhas || nw || pend_ok)) break;
@@ -2301,7 +2143,6 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     const Params &p_kernel = p;
     const Params p = HTTP ? *pa : p_kernel;   /* the phr kernels had no such spills (config 3 +1-3 % with the reload) */
 #endif
-    typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
     /* what a request needs first: in http mode the hint left in its http
      * record says what to do (and holds ret), so neither the request record is
      * read nor its flags written back.  Pass 1 fetches it one request ahead. */
@@ -2458,26 +2299,17 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
      * workgroup's end set by its slowest wave), so the faster waves take more
      * rounds (round 5) */
     uint32_t *round_next = wg_counter + 2;   /* entries claimed; 0 since the prologue */
-    /* A round is at most 64 entries (one per lane).  Near the end of the range
-     * the rounds shrink (32, then 16 entries: RHP_TAIL_ROUNDS), so the last ones
-     * -- a 64-body round of chunked moves is ~150 us of one wave -- end closer
-     * together; a wave judges "near the end" from its own last claim */
-    auto claim = [&](uint32_t last) -> uint2 {
-      uint32_t want = 64u;
-#ifdef RHP_TAIL_ROUNDS
-      const uint32_t left = ns > last ? ns - last : 0u;
-      want = left > 32u * WAVES * 2u ? 64u : left > 16u * WAVES * 2u ? 32u : 16u;
-#endif
-      (void) last;
+    /* a round is 64 entries (one per lane) */
+    auto claim = [&]() -> uint2 {
       uint32_t r = 0;
-      if (lane == 0) r = atomicAdd(round_next, want);
+      if (lane == 0) r = atomicAdd(round_next, 64u);
       r = __builtin_amdgcn_readfirstlane(r);
-      return uint2{r, min(r + want, ns)};
+      return uint2{r, min(r + 64u, ns)};
     };
-    uint2 kr = claim(0u);
+    uint2 kr = claim();
     if (kr.x < ns) start_round(kr.x, kr.y);
     while (kr.x < ns) {
-      const uint2 kn = claim(kr.y);
+      const uint2 kn = claim();
       if constexpr (http) {
         dg.part_begin();
         while (__builtin_amdgcn_ballot_w64(w.live)) w.step();   /* what the last round's moves left */
@@ -2606,11 +2438,9 @@ int device_cus(int dev, int *cus)
 template <int WAVES, bool LATE, bool HTTP, int REC>
 int launch_dfa(const Params &prm, hipStream_t s, int dev, int cus)
 {
-  constexpr uint32_t kX = (LATE && HTTP) ? kHttpXParts : 0u;
   /* table, staging, pool area, the order's bucket cursors past it (the kernel's
-   * `bucket`), the extension parts: one sum for the launch and the check */
-  constexpr size_t lds_bytes = kLdsTable + (size_t) WAVES * kStageWave + kPoolBytes + 4u * kOrderBuckets +
-                               (size_t) WAVES * 1024u * kX;
+   * `bucket`): one sum for the launch and the check */
+  constexpr size_t lds_bytes = kLdsTable + (size_t) WAVES * kStageWave + kPoolBytes + 4u * kOrderBuckets;
   static_assert(lds_bytes <= 160u * 1024u, "the workgroup's LDS fits the CU's 160 KiB");
   const uint64_t bit = 1ull << ((3 * (WAVES / 4) + REC) * 4 + (LATE ? 2 : 0) + (HTTP ? 1 : 0));   /* < 64: WAVES 8/12/16 */
   if (!(g_attr[dev].load(std::memory_order_acquire) & bit)) {
@@ -2631,14 +2461,29 @@ int launch_dfa(const Params &prm, hipStream_t s, int dev, int cus)
   return (int) hipGetLastError();
 }
 
-/* waves per workgroup of the phr-mode kernels (16: four per SIMD) */
-#ifndef RHP_PHR_WAVES
-#define RHP_PHR_WAVES 16
-#endif
-
 /* the late-issue form: http mode (frames requests in the loop), or on request
  * (RHP_IMPL_DFA_LATE, parity tests of that form in phr mode) */
 bool late_issue(uint32_t mode) { return t_impl == RHP_IMPL_DFA_LATE || mode == RHP_MODE_HTTP; }
+
+/* what every launch takes from the batch: its buffers, and rhp_hdr_t records
+ * in its request- or header-major layout (everything else zero) */
+Params batch_params(const rhp_batch_t *b)
+{
+  Params prm = {};
+  prm.bytes = b->bytes;
+  prm.bytes_rw = b->bytes_rw;
+  prm.offsets = b->offsets;
+  prm.reqs = b->reqs;
+  prm.hdrs = b->hdrs;
+  prm.http = b->http;
+  prm.n = b->n;
+  prm.max_headers = b->max_headers;
+  prm.mode = b->mode;
+  const bool hmajor = b->layout == RHP_LAYOUT_HEADER_MAJOR;
+  prm.rec_req = prm.hs_req = hmajor ? 1u : b->max_headers;
+  prm.rec_hdr = prm.hs_hdr = hmajor ? b->n : 1u;
+  return prm;
+}
 }  // namespace
 
 extern "C" {
@@ -2696,33 +2541,13 @@ int rhp_parse_batch(const rhp_batch_t *b, void *stream)
     if (rc != 0) return rc;
   }
 
-  Params prm;
-  prm.bytes = b->bytes;
-  prm.bytes_rw = b->bytes_rw;
-  prm.offsets = b->offsets;
-  prm.reqs = b->reqs;
-  prm.hdrs = b->hdrs;
-  prm.http = b->http;
-  prm.last_len = b->last_len;
-  prm.compact = !(b->flags & RHP_BATCH_SPECULATIVE);
-  prm.n = b->n;
-  prm.max_headers = b->max_headers;
-  prm.mode = b->mode;
-  prm.span = 0;
-  const bool hmajor = b->layout == RHP_LAYOUT_HEADER_MAJOR;
   const bool compact = b->layout == RHP_LAYOUT_COMPACT;
   const bool dense = b->layout == RHP_LAYOUT_DENSE || b->layout == RHP_LAYOUT_DENSE_RM;
   if (dense && (b->mode == RHP_MODE_HTTP ? b->layout != RHP_LAYOUT_DENSE || (b->flags & RHP_BATCH_SPECULATIVE) : false))
     return -22;   /* http mode: header-major dense records, not speculative */
-  prm.hs_req = hmajor ? 1u : b->max_headers;
-  prm.hs_hdr = hmajor ? b->n : 1u;
-  prm.lens = nullptr;
-  prm.hc = nullptr;
-  prm.dreq = nullptr;
-  prm.lens16 = nullptr;
-  prm.ovf32 = nullptr;
-  prm.rec_req = prm.hs_req;
-  prm.rec_hdr = prm.hs_hdr;
+  Params prm = batch_params(b);
+  prm.last_len = b->last_len;
+  prm.compact = !(b->flags & RHP_BATCH_SPECULATIVE);
   prm.wt_records = b->mode == RHP_MODE_PHR && b->layout != RHP_LAYOUT_REQUEST_MAJOR && b->layout != RHP_LAYOUT_DENSE_RM;
   if (dense) {   /* 8-byte request records and u16 lengths (header-major), the wide ones behind them */
     prm.dreq = reinterpret_cast<uint2 *>(b->reqs);
@@ -2791,24 +2616,8 @@ int rhp_fixup_sessions(const rhp_batch_t *b, const rhp_session_t *sessions, uint
   if (!b->bytes_rw || !b->offsets || !b->reqs || !b->http || (b->max_headers && !b->hdrs)) return -22;
   if (b->layout != RHP_LAYOUT_REQUEST_MAJOR && b->layout != RHP_LAYOUT_HEADER_MAJOR) return -22;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  Params prm = {};
-  prm.bytes = b->bytes;
-  prm.bytes_rw = b->bytes_rw;
-  prm.offsets = b->offsets;
-  prm.reqs = b->reqs;
-  prm.hdrs = b->hdrs;
-  prm.http = b->http;
-  prm.n = b->n;
-  prm.max_headers = b->max_headers;
-  prm.mode = b->mode;
+  Params prm = batch_params(b);
   prm.compact = true;
-  const bool hmajor = b->layout == RHP_LAYOUT_HEADER_MAJOR;
-  prm.hs_req = hmajor ? 1u : b->max_headers;
-  prm.hs_hdr = hmajor ? b->n : 1u;
-  prm.lens = nullptr;
-  prm.rec_req = prm.hs_req;
-  prm.rec_hdr = prm.hs_hdr;
-  prm.wt_records = false;
   const uint32_t grid = (n_sessions + 3u) / 4u;   /* four sessions (waves) per workgroup */
   hipLaunchKernelGGL(rhp_fixup_kernel, dim3(grid), dim3(256), 0, s, prm, sessions, n_sessions, results, req_start);
   return (int) hipGetLastError();
