@@ -83,9 +83,12 @@ enum rhp_layout {
   RHP_LAYOUT_HEADER_MAJOR = 1,
   RHP_LAYOUT_COMPACT = 2,     /* 4-byte header records, below (http mode: 8-byte http records too;
                                  not with RHP_BATCH_SPECULATIVE) */
-  RHP_LAYOUT_DENSE = 3,       /* 8-byte request and 2-byte header records, below (both modes; http
-                                 mode: the 8-byte http records too; not with RHP_BATCH_SPECULATIVE) */
-  RHP_LAYOUT_DENSE_RM = 4     /* the same, the header records request-major (RHP_MODE_PHR only) */
+  RHP_LAYOUT_DENSE = 3,       /* 8-byte request and 2-byte header records, below (both modes; in
+                                 RHP_MODE_HTTP the http records are the compact ones and `http`
+                                 holds RHP_COMPACT_HTTP_BYTES(n) bytes; not with
+                                 RHP_BATCH_SPECULATIVE) */
+  RHP_LAYOUT_DENSE_RM = 4     /* the same, the header records request-major (RHP_MODE_PHR only:
+                                 refused in RHP_MODE_HTTP) */
 };
 /* Compact records (RHP_LAYOUT_COMPACT).  A header line the DFA
  * parses is `name ": " value CRLF` and the first one starts right after the
@@ -122,7 +125,9 @@ enum rhp_layout {
  * RHP_DENSE_WIDE, its records are wide[i] and the wide header records.
  * RHP_DENSE_BAD: ret = -1 (the other outputs unspecified, as in rhp_req_t).
  * Config 2 writes 8 + 4 x 2 = 16 B of records per request (compact: 32 B).
- * rhp_expand_reqs / rhp_expand_records (rhp_host.h) expand them on the host. */
+ * rhp_expand_reqs / rhp_expand_records / rhp_expand_http (rhp_host.h) expand
+ * them on the host; rhp_records.h states every encoding and area of this file
+ * once, as inline C (its decoders are what a C consumer calls). */
 typedef struct rhp_req_dense {
   uint16_t ret;           /* 1..65535 (the header section), when neither flag is set */
   uint16_t path_len;

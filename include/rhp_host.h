@@ -1,5 +1,7 @@
 /*
- * rhp_host.h -- host-side entry points of librhp_host.so (no GPU).
+ * rhp_host.h -- host-side entry points of librhp_host.so (no GPU): the
+ * product's (csrc/rhp_host.cpp; libreactor.so links them) and, for tests, the
+ * DFA emulator and the rhp_test_* hooks (csrc/rhp_emu.cpp).
  *
  *   rhp_cpu_parse_batch   the product's exact scalar parser (rhp_scalar.h, the
  *                         same code the kernel's rare paths run) over a batch in
@@ -7,10 +9,14 @@
  *                         "host" session parser use it
  *   rhp_emu_parse_batch   CPU emulation of the kernel's DFA algorithm, block for
  *                         block (tests only); stats[3] = fast ok, fast -1, exact
- *   (both take an rhp_batch_t (include/rhp.h) whose pointers are host memory)
+ *   (both take an rhp_batch_t (include/rhp.h) whose pointers are host memory,
+ *   of any alignment, and refuse with -22 what rhp_parse_batch refuses:
+ *   rhp_records.h rhp_batch_check)
  *   rhp_expand_records    any layout's header records (the compact and dense
  *                         ones included) as rhp_hdr_t, on the host;
- *   rhp_expand_reqs       the dense layout's request records as rhp_req_t
+ *   rhp_expand_reqs       the dense layouts' request records as rhp_req_t
+ *   rhp_expand_http       the compact http records (RHP_LAYOUT_COMPACT and
+ *                         RHP_LAYOUT_DENSE) as rhp_http_t
  *   rhp_cpu_classify_batch  rhp_classify_batch (rhp.h) over a parsed batch in
  *                         host memory, written over the three rhp_expand_*
  *
@@ -64,8 +70,9 @@ int rhp_expand_records(const rhp_batch_t *batch, const rhp_req_t *reqs, const vo
  * requests first: rhp_expand_records and rhp_expand_http take rhp_req_t. */
 int rhp_expand_reqs(const rhp_batch_t *batch, const void *reqs, rhp_req_t *out);
 /* A batch's http records (RHP_MODE_HTTP) as rhp_http_t[n]: copied, or for
- * RHP_LAYOUT_COMPACT and RHP_LAYOUT_DENSE expanded from the compact records and their wide area
- * (rhp.h rhp_http_compact_t; consumed from reqs[i].ret).  0, or -22. */
+ * RHP_LAYOUT_COMPACT and RHP_LAYOUT_DENSE (both hold RHP_COMPACT_HTTP_BYTES(n)
+ * bytes) expanded from the compact records and their wide area (rhp.h
+ * rhp_http_compact_t; consumed from reqs[i].ret).  0, or -22. */
 int rhp_expand_http(const rhp_batch_t *batch, const rhp_req_t *reqs, const void *http, rhp_http_t *out);
 
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */

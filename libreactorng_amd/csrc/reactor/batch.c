@@ -41,6 +41,7 @@
 #include "reactor.h"
 #include "reactor_batch.h"
 #include "rhp.h"
+#include "rhp_records.h"
 #include "rhp_host.h"
 
 enum { PARSER_UNSET, PARSER_GPU, PARSER_HOST, PARSER_HOST_ASYNC };
@@ -743,43 +744,23 @@ void reactor_batch_record(const reactor_batch_result_t *r, uint32_t i, rhp_req_t
     *hp = r->hdrs + (size_t) i * REACTOR_BATCH_HEADERS;
     return;
   }
+  /* the dense copies (rhp_records.h): a wide http record is the batch's own,
+   * and so are the request and its header records of a wide request that is
+   * ready (the round fetched them: reactor_batch_result); any other wide
+   * request has no record here and decodes as ret 0 */
   const rhp_http_compact_t c = r->hc[i];
   const rhp_req_dense_t d = r->dreq[i];
   const int result = c.flags & RHP_HTTP_WIDE ? r->http[i].result : c.result;
   const bool rw = result == 1 && (d.flags & RHP_DENSE_WIDE);
-  if (rw)
+  *req = rhp_req_dense_decode(d, rw ? &r->reqs[i] : NULL);
+  *hp = rw ? r->hdrs + (size_t) i * REACTOR_BATCH_HEADERS : h;
+  if (!rw && result == 1)
   {
-    *req = r->reqs[i];
-    *hp = r->hdrs + (size_t) i * REACTOR_BATCH_HEADERS;
+    uint32_t at = rhp_hdr_first(req);
+    for (uint32_t k = 0; k < d.num_headers; k++)
+      h[k] = rhp_hdr_next(&at, rhp_len16_unpack(r->lens16[(size_t) k * r->n + i]));
   }
-  else
-  {
-    /* rhp.h dense records: path_off = method_len + 1, the header offsets a running sum */
-    memset(req, 0, sizeof *req);
-    req->ret = d.ret;
-    req->method_len = d.method_len;
-    req->path_off = (uint16_t) (d.method_len + 1u);
-    req->path_len = d.path_len;
-    req->minor_version = (int8_t) d.minor_version;
-    req->num_headers = d.num_headers;
-    uint32_t at = (uint32_t) req->path_off + req->path_len + 11u;
-    for (uint32_t k = 0; k < d.num_headers && result == 1; k++)
-    {
-      const uint32_t l = r->lens16[(size_t) k * r->n + i], nl = l & 63u, vl = l >> 6;
-      h[k] = (rhp_hdr_t) {(uint16_t) at, (uint16_t) nl, (uint16_t) (at + nl + 2u), (uint16_t) vl};
-      at += nl + vl + 4u;
-    }
-    *hp = h;
-  }
-  if (c.flags & RHP_HTTP_WIDE)
-    *x = r->http[i];
-  else
-  {
-    x->result = c.result;
-    x->body_kind = c.body_kind;
-    x->body_len = c.body_len;
-    x->consumed = c.result == 1 ? (uint64_t) (uint32_t) req->ret + (c.body_kind == 1 ? c.body_len : 0u) : 0u;
-  }
+  *x = rhp_http_compact_decode(c, req->ret, &r->http[i]);
 }
 
 enum { WRITER_HOST, WRITER_HOST_BATCH, WRITER_GPU };

@@ -1,0 +1,287 @@
+/*
+ * rhp_host.cpp -- the product's host entry points (rhp_host.h): the exact
+ * scalar parser over a batch in host memory, the session fix-up, the dense
+ * pack and the three expansions, the host classify, and the pointer-based
+ * rhp_phr_parse_request / rhp_http_read_cpu.  libreactor.so links them.  The
+ * parser is rhp_scalar.h's (the code the kernel's rare paths run); where the
+ * records sit and how they are encoded is rhp_records.h's.
+ */
+#include <stdint.h>
+#include <string.h>
+#include <vector>
+
+#include "rhp.h"
+#include "rhp_host.h"
+#include "rhp_records.h"
+#include "rhp_scalar.h"
+#include "rhp_classify_args.h"
+#include "rhp_host_exact.h"
+
+using namespace rhp;
+
+void rhp::host_put_http(const rhp_view_t &v, uint32_t i, const rhp_http_t &x, bool wide)
+{
+  if (!v.hc) {
+    v.http[i] = x;
+    return;
+  }
+  if (wide) v.http[i] = x;
+  v.hc[i] = rhp_http_compact_encode(&x, wide);
+}
+
+void rhp::host_exact(const rhp_batch_t *b, const rhp_view_t &v, uint32_t i, uint64_t off, uint64_t len)
+{
+  rhp_req_t r;
+  /* a length layout: the exact path's records are the wide ones */
+  r.flags = RHP_F_EXACT | (rhp_layout_lens(b->layout) ? RHP_F_WIDE : 0u);
+  rhp_hdr_t *h = v.hdrs + i * v.hs_req;
+  if (b->mode == RHP_MODE_HTTP) {
+    PlainBytes B{b->bytes_rw + off};
+    rhp_http_t x;
+    scalar_http_t(B, b->bytes_rw + off, len, b->max_headers, &r, h, v.hs_hdr, &x, !(b->flags & RHP_BATCH_SPECULATIVE));
+    host_put_http(v, i, x, true);
+  }
+  else {
+    const uint64_t ll = b->last_len ? b->last_len[i] : 0;
+    const int pre = ll ? is_complete(b->bytes + off, len, ll) : 0;   /* picohttpparser.c:399-401 */
+    if (pre != 0) {
+      const uint16_t flags = r.flags;
+      memset(&r, 0, sizeof r);
+      r.ret = pre;
+      r.minor_version = -1;
+      r.flags = flags;
+    } else {
+      scalar_phr(b->bytes + off, len, b->max_headers, &r, h, v.hs_hdr);
+    }
+  }
+  v.reqs[i] = r;
+  if (v.dreq) v.dreq[i] = rhp_req_dense_mark(RHP_DENSE_WIDE);
+}
+
+/* The exact scalar path alone, on the host (the product's CPU parser): in a
+ * length layout every record is a wide one. */
+extern "C" int rhp_cpu_parse_batch(const rhp_batch_t *b)
+{
+  if (rhp_batch_check(b, 0) < 0) return -22;
+  const rhp_view_t v = rhp_batch_view(b);
+  for (uint32_t i = 0; i < b->n; i++) host_exact(b, v, i, b->offsets[i], b->offsets[i + 1] - b->offsets[i]);
+  return 0;
+}
+
+/* rhp_fixup_sessions (rhp.h) on the host: the same walk (rhp_scalar.h
+ * fixup_session_t) over a speculative batch parsed by rhp_cpu_parse_batch or
+ * rhp_emu_parse_batch. */
+extern "C" int rhp_cpu_fixup_sessions(const rhp_batch_t *b, const rhp_session_t *sessions, uint32_t n_sessions,
+                                      rhp_session_result_t *results, uint64_t *req_start)
+{
+  if (!b || b->mode != RHP_MODE_HTTP || !(b->flags & RHP_BATCH_SPECULATIVE)) return -22;
+  const rhp_view_t v = rhp_batch_view(b);
+  const FixupIO io{b->bytes_rw, b->offsets, v.reqs, v.hdrs, v.http, v.hs_req, v.hs_hdr, b->max_headers};
+  for (uint32_t k = 0; k < n_sessions; k++)
+    fixup_session_t(io, sessions[k].piece_lo, sessions[k].piece_hi, req_start, &results[k],
+                    [&](uint64_t at) { return PlainBytes{b->bytes_rw + at}; });
+  return 0;
+}
+
+extern "C" int rhp_expand_reqs(const rhp_batch_t *b, const void *reqs, rhp_req_t *out)
+{
+  if (!b || !reqs || !out) return -22;
+  const rhp_view_t v = rhp_view(reqs, nullptr, nullptr, b->n, b->max_headers, b->mode, b->layout);
+  if (!v.dreq) {
+    memcpy(out, reqs, sizeof(rhp_req_t) * b->n);
+    return 0;
+  }
+  for (uint32_t i = 0; i < b->n; i++) out[i] = rhp_req_dense_decode(v.dreq[i], &v.reqs[i]);
+  return 0;
+}
+
+extern "C" int rhp_expand_records(const rhp_batch_t *b, const rhp_req_t *reqs, const void *hdrs, rhp_hdr_t *out)
+{
+  if (!b || !reqs || !out || (b->max_headers && !hdrs)) return -22;
+  if (b->layout > RHP_LAYOUT_DENSE_RM) return -22;
+  const uint32_t n = b->n, m = b->max_headers;
+  const rhp_view_t v = rhp_view(nullptr, hdrs, nullptr, n, m, b->mode, b->layout);
+  const bool lens = rhp_layout_lens(b->layout);
+  for (uint32_t i = 0; i < n; i++) {
+    rhp_hdr_t *o = out + (uint64_t) i * m;
+    memset(o, 0, sizeof(rhp_hdr_t) * m);
+    const rhp_req_t &r = reqs[i];
+    if (r.ret <= 0) continue;
+    const uint32_t nh = r.num_headers < m ? r.num_headers : m;
+    if (lens && !(r.flags & RHP_F_WIDE)) {
+      uint32_t at = rhp_hdr_first(&r);
+      for (uint32_t k = 0; k < nh; k++) o[k] = rhp_hdr_next(&at, rhp_view_len32(&v, i, k));
+    } else {
+      for (uint32_t k = 0; k < nh; k++) o[k] = v.hdrs[i * v.hs_req + k * v.hs_hdr];
+    }
+  }
+  return 0;
+}
+
+extern "C" int rhp_expand_http(const rhp_batch_t *b, const rhp_req_t *reqs, const void *http, rhp_http_t *out)
+{
+  if (!b || !reqs || !http || !out) return -22;
+  /* the http records are what the layout says in RHP_MODE_HTTP, whatever mode `b` names */
+  const rhp_view_t v = rhp_view(nullptr, nullptr, http, b->n, b->max_headers, RHP_MODE_HTTP, b->layout);
+  if (!v.hc) {
+    memcpy(out, http, sizeof(rhp_http_t) * b->n);
+    return 0;
+  }
+  for (uint32_t i = 0; i < b->n; i++) out[i] = rhp_http_compact_decode(v.hc[i], reqs[i].ret, &v.http[i]);
+  return 0;
+}
+
+/* rhp_pack_dense (rhp.h) on the host: rhp_pack_dense_one per record slot, as
+ * the kernel (rhp_kernel.hip rhp_pack_dense_kernel), for the reactor's
+ * host-async parser */
+extern "C" int rhp_cpu_pack_dense(const rhp_batch_t *b, rhp_req_dense_t *dreq, rhp_http_compact_t *hc, uint16_t *lens16)
+{
+  if (!b || b->mode != RHP_MODE_HTTP || b->layout != RHP_LAYOUT_REQUEST_MAJOR || b->max_headers > RHP_MAX_HEADERS) return -22;
+  const uint32_t n = b->n, m = b->max_headers;
+  for (uint32_t i = 0; i < n; i++)
+    dreq[i] = rhp_pack_dense_one(&b->reqs[i], &b->http[i], b->hdrs + (uint64_t) i * m, m, lens16 + i, n, &hc[i]);
+  return 0;
+}
+
+/* rhp_classify_batch (rhp.h) on the host, over a parsed batch in host memory:
+ * http_field_lookup (src/reactor/http.c:167-175: the first field whose name is
+ * string_equal_case, src/reactor/data.c:11-28) per name and the first route
+ * whose target and method are string_equal, one request and one byte at a
+ * time over the records as rhp_expand_reqs / rhp_expand_records /
+ * rhp_expand_http give them -- a decode of the layouts that shares nothing
+ * with the kernel's (rhp_classify.hip). */
+extern "C" int rhp_cpu_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c)
+{
+  const int rc = rhp_classify_check(b, c);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const uint32_t n = b->n, m = b->max_headers;
+  const bool http_mode = b->mode == RHP_MODE_HTTP;
+  std::vector<rhp_req_t> reqs(n);
+  std::vector<rhp_hdr_t> hdrs((size_t) n * m);
+  std::vector<rhp_http_t> http(http_mode ? n : 0);
+  if (rhp_expand_reqs(b, b->reqs, reqs.data()) != 0) return -22;
+  if (m && rhp_expand_records(b, reqs.data(), b->hdrs, hdrs.data()) != 0) return -22;
+  if (http_mode && rhp_expand_http(b, reqs.data(), b->http, http.data()) != 0) return -22;
+  const uint8_t *bytes = http_mode && b->bytes_rw ? b->bytes_rw : b->bytes;
+  const auto upper = [](uint8_t x) { return x >= 'a' && x <= 'z' ? (uint8_t) (x - ('a' - 'A')) : x; };   /* C-locale toupper */
+  const auto same = [&](const uint8_t *s, uint32_t len, rhp_span_t t) {
+    return len == t.len && (len == 0 || memcmp(s, c->text + t.off, len) == 0);
+  };
+  for (uint32_t i = 0; i < n; i++) {
+    const rhp_req_t &r = reqs[i];
+    const bool ready = r.ret > 0 && (!http_mode || http[i].result == 1);
+    const uint8_t *req = bytes + b->offsets[i];
+    const uint32_t nh = !ready ? 0u : r.num_headers < m ? r.num_headers : m;
+    for (uint32_t j = 0; j < c->n_names; j++) {
+      const uint8_t *name = c->text + c->names[j].off;
+      const uint32_t len = c->names[j].len;
+      rhp_fieldref_t f = {RHP_NAME_NULL, 0};
+      for (uint32_t k = 0; k < nh; k++) {
+        const rhp_hdr_t &h = hdrs[(size_t) i * m + k];
+        if (h.name_off == RHP_NAME_NULL || h.name_len != len) continue;
+        uint32_t q = 0;
+        while (q < len && upper(req[h.name_off + q]) == upper(name[q])) q++;
+        if (q == len) {
+          f = rhp_fieldref_t{h.value_off, h.value_len};
+          break;
+        }
+      }
+      c->fields[(size_t) j * n + i] = f;
+    }
+    if (!c->route) continue;
+    uint16_t rt = RHP_ROUTE_NONE;
+    for (uint32_t k = 0; ready && k < c->n_routes; k++) {
+      const rhp_route_t &t = c->routes[k];
+      if (same(req + r.path_off, r.path_len, t.target) && (t.method.len == 0 || same(req + r.method_off, r.method_len, t.method))) {
+        rt = (uint16_t) k;
+        break;
+      }
+    }
+    c->route[i] = rt;
+  }
+  return 0;
+}
+
+/* ---- the pointer-based host parser: phr_parse_request's own outputs ---- */
+
+namespace {
+
+/* rhp_scalar.h output policy writing phr_parse_request's outputs (pointers
+ * into buf, size_t lengths): no length limit */
+struct OutPhr {
+  const uint8_t *base;
+  const char **method;
+  size_t *method_len;
+  const char **path;
+  size_t *path_len;
+  int *minor_version;
+  rhp_phr_header_t *h;
+  size_t *num_headers;
+  void begin()
+  {
+    *method = nullptr; *method_len = 0; *path = nullptr; *path_len = 0;   /* picohttpparser.c:390-395 */
+    *minor_version = -1; *num_headers = 0;
+  }
+  int fail(int code) { return code; }
+  void header(uint32_t n, bool fold, uint64_t name, uint64_t name_len, uint64_t vs, uint64_t vlen)
+  {
+    h[n].name = fold ? nullptr : (const char *) base + name;
+    h[n].name_len = (size_t) name_len;
+    h[n].value = (const char *) base + vs;
+    h[n].value_len = (size_t) vlen;
+  }
+  int done(uint64_t p, const uint64_t (&tok)[2][2], int minor, uint32_t n)
+  {
+    *method = (const char *) base + tok[0][0];
+    *method_len = (size_t) (tok[0][1] - tok[0][0]);
+    *path = (const char *) base + tok[1][0];
+    *path_len = (size_t) (tok[1][1] - tok[1][0]);
+    *minor_version = minor;
+    *num_headers = n;
+    return (int) p;
+  }
+};
+
+/* rhp_scalar.h header view over phr_header records */
+struct HdrsPhr {
+  const rhp_phr_header_t *h;
+  bool null(uint32_t i) const { return h[i].name == nullptr; }
+  const uint8_t *name(uint32_t i) const { return (const uint8_t *) h[i].name; }
+  uint64_t name_len(uint32_t i) const { return h[i].name_len; }
+  const uint8_t *value(uint32_t i) const { return (const uint8_t *) h[i].value; }
+  uint64_t value_len(uint32_t i) const { return h[i].value_len; }
+};
+
+}  // namespace
+
+extern "C" int rhp_phr_parse_request(const char *buf, size_t len, const char **method, size_t *method_len,
+                                     const char **path, size_t *path_len, int *minor_version,
+                                     rhp_phr_header_t *headers, size_t *num_headers, size_t last_len)
+{
+  const uint8_t *b = (const uint8_t *) buf;
+  const size_t max = *num_headers;
+  OutPhr o{b, method, method_len, path, path_len, minor_version, headers, num_headers};
+  if (last_len != 0) {   /* picohttpparser.c:399-401 */
+    o.begin();
+    const int r = is_complete(b, len, last_len);
+    if (r != 0) return r;
+  }
+  PlainBytes B{b};
+  return scalar_phr_t(B, len, (uint32_t) (max < 0xffffffffu ? max : 0xffffffffu), o);
+}
+
+extern "C" int rhp_http_read_cpu(uint8_t *buf, size_t len, rhp_http_req_t *req, rhp_phr_header_t *fields,
+                                 size_t *fields_count)
+{
+  if (len == 0) return 0;                               /* http.c:184-186 */
+  const int n = rhp_phr_parse_request((const char *) buf, len, &req->method, &req->method_len, &req->target,
+                                      &req->target_len, &req->minor_version, fields, fields_count, 0);
+  if (n <= 0) return n == kBad ? -1 : 0;                /* http.c:194-195 */
+  const bool get = req->method_len == 3 && memcmp(req->method, "GET", 3) == 0;
+  rhp_http_t x;
+  http_frame_t(buf, len, n, get, HdrsPhr{fields}, (uint32_t) *fields_count, &x);
+  req->body = x.body_kind ? buf + n : nullptr;
+  req->body_len = x.body_kind ? (size_t) x.body_len : 0;
+  req->consumed = x.consumed;
+  return x.result;
+}

@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "rhp.h"
+#include "rhp_records.h"
 #include "rhp_dfa.h"
 #include "rhp_scalar.h"
 
@@ -2335,7 +2336,8 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
 }
 
 /* rhp_pack_dense (rhp.h): one thread per record slot, the dense encodings of
- * its request-major records (the host expands them: reactor/batch.c) */
+ * its request-major records (rhp_records.h rhp_pack_dense_one; the host expands
+ * them: reactor/batch.c).  The two 8-byte records leave as one store each. */
 __global__ __launch_bounds__(256) void rhp_pack_dense_kernel(const rhp_req_t *reqs, const rhp_hdr_t *hdrs,
                                                              const rhp_http_t *http, uint32_t n, uint32_t m, uint2 *dreq,
                                                              uint2 *hc, uint16_t *lens16)
@@ -2344,27 +2346,14 @@ __global__ __launch_bounds__(256) void rhp_pack_dense_kernel(const rhp_req_t *re
   if (i >= n) return;
   const rhp_req_t r = reqs[i];
   const rhp_http_t x = http[i];
-  /* the http record: compact when its consumed follows from ret (rhp.h) */
-  const uint64_t cons = x.result == 1 ? (uint64_t) (uint32_t) r.ret + (x.body_kind == 1 ? x.body_len : 0u) : 0u;
-  const bool hok = x.consumed == cons && x.body_kind <= 1u && !(x.body_len >> 32) && (x.result != 1 || r.ret > 0);
-  hc[i] = hok ? uint2{((uint32_t) x.result & 0xffu) | x.body_kind << 8, (uint32_t) x.body_len} : uint2{RHP_HTTP_WIDE << 16, 0u};
-  /* the request: dense when the DFA's regular form holds it and the http
-   * record is compact (a de-framed chunked body moves its request's bytes:
-   * the wide records' offsets are the moved ones) */
-  bool reg = hok && x.result == 1 && r.ret > 0 && r.ret <= (int32_t) RHP_MAX_LEN && r.method_off == 0 && r.method_len <= 255u &&
-             r.path_off == r.method_len + 1u && r.num_headers <= m;
-  uint32_t at = (uint32_t) r.path_off + r.path_len + 11u;
-  const uint32_t nh = reg ? r.num_headers : 0u;
-  for (uint32_t k = 0; k < nh; k++) {
-    const rhp_hdr_t h = hdrs[(uint64_t) i * m + k];
-    reg = reg && h.name_off == at && h.value_off == at + h.name_len + 2u &&
-          max((uint32_t) h.name_len << 4, (uint32_t) h.value_len) <= RHP_DENSE_VALUE_MAX;
-    at += (uint32_t) h.name_len + h.value_len + 4u;
-    lens16[(uint64_t) k * n + i] = (uint16_t) (h.name_len | (uint32_t) h.value_len << 6);
-  }
-  dreq[i] = reg ? uint2{(uint32_t) r.ret | (uint32_t) r.path_len << 16,
-                        r.method_len | (uint32_t) r.num_headers << 8 | ((uint32_t) (uint8_t) r.minor_version) << 16}
-                : uint2{0u, RHP_DENSE_WIDE << 24};
+  rhp_http_compact_t c;
+  const rhp_req_dense_t d = rhp_pack_dense_one(&r, &x, hdrs + (uint64_t) i * m, m, lens16 + i, n, &c);
+  static_assert(sizeof d == sizeof(uint2) && sizeof c == sizeof(uint2), "8-byte records");
+  uint2 w;
+  memcpy(&w, &c, sizeof w);
+  hc[i] = w;
+  memcpy(&w, &d, sizeof w);
+  dreq[i] = w;
 }
 
 /* rhp_fixup_sessions: one wave per session.  The wave first takes the
@@ -2465,23 +2454,30 @@ int launch_dfa(const Params &prm, hipStream_t s, int dev, int cus)
  * (RHP_IMPL_DFA_LATE, parity tests of that form in phr mode) */
 bool late_issue(uint32_t mode) { return t_impl == RHP_IMPL_DFA_LATE || mode == RHP_MODE_HTTP; }
 
-/* what every launch takes from the batch: its buffers, and rhp_hdr_t records
- * in its request- or header-major layout (everything else zero) */
+/* what every launch takes from the batch: its buffers, and where its layout
+ * has each kind of record (rhp_records.h rhp_view_t; everything else zero) */
 Params batch_params(const rhp_batch_t *b)
 {
+  const rhp_view_t v = rhp_batch_view(b);
   Params prm = {};
   prm.bytes = b->bytes;
   prm.bytes_rw = b->bytes_rw;
   prm.offsets = b->offsets;
-  prm.reqs = b->reqs;
-  prm.hdrs = b->hdrs;
-  prm.http = b->http;
   prm.n = b->n;
   prm.max_headers = b->max_headers;
   prm.mode = b->mode;
-  const bool hmajor = b->layout == RHP_LAYOUT_HEADER_MAJOR;
-  prm.rec_req = prm.hs_req = hmajor ? 1u : b->max_headers;
-  prm.rec_hdr = prm.hs_hdr = hmajor ? b->n : 1u;
+  prm.reqs = v.reqs;
+  prm.hdrs = v.hdrs;
+  prm.http = v.http;
+  prm.hs_req = (uint32_t) v.hs_req;
+  prm.hs_hdr = (uint32_t) v.hs_hdr;
+  prm.lens = v.lens;
+  prm.rec_req = (uint32_t) v.rec_req;
+  prm.rec_hdr = (uint32_t) v.rec_hdr;
+  prm.hc = reinterpret_cast<uint2 *>(v.hc);
+  prm.dreq = reinterpret_cast<uint2 *>(v.dreq);
+  prm.lens16 = v.lens16;
+  prm.ovf32 = v.ovf32;
   return prm;
 }
 }  // namespace
@@ -2517,20 +2513,8 @@ int rhp_set_impl(int impl)
 int rhp_parse_batch(const rhp_batch_t *b, void *stream)
 {
   if (!b) return -22;
-  if (b->n == 0) return 0;                       /* nothing to parse, nothing touched */
-  if (!b->bytes || !b->offsets || !b->reqs) return -22;
-  if (((uintptr_t) b->bytes & 15u) != 0) return -22;   /* windows and exact-path lines are aligned loads */
-  if (b->max_headers > RHP_MAX_HEADERS) return -22;
-  if (b->max_headers > 0 && !b->hdrs) return -22;
-  if ((uint64_t) b->n * b->max_headers > 0xffffffffull) return -22;   /* record indices are 32-bit */
-  if (b->mode == RHP_MODE_HTTP && (!b->http || !b->bytes_rw)) return -22;
-  if (b->mode != RHP_MODE_PHR && b->mode != RHP_MODE_HTTP) return -22;
-  if (b->layout != RHP_LAYOUT_REQUEST_MAJOR && b->layout != RHP_LAYOUT_HEADER_MAJOR &&
-      !(b->layout == RHP_LAYOUT_COMPACT && !(b->flags & RHP_BATCH_SPECULATIVE)) &&
-      !(b->layout == RHP_LAYOUT_DENSE || b->layout == RHP_LAYOUT_DENSE_RM))
-    return -22;   /* compact: not speculative; dense: below */
-  if (b->last_len && b->mode != RHP_MODE_PHR) return -22;   /* http_read_request passes last_len 0 */
-  if ((b->flags & ~RHP_BATCH_SPECULATIVE) || ((b->flags & RHP_BATCH_SPECULATIVE) && b->mode != RHP_MODE_HTTP)) return -22;
+  if (b->n == 0) return 0;   /* nothing to parse, nothing touched: before any rule (rhp_batch_check has the rules first) */
+  if (rhp_batch_check(b, 1) != 0) return -22;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int dev = 0, cus = 0;
   {
@@ -2541,40 +2525,11 @@ int rhp_parse_batch(const rhp_batch_t *b, void *stream)
     if (rc != 0) return rc;
   }
 
-  const bool compact = b->layout == RHP_LAYOUT_COMPACT;
-  const bool dense = b->layout == RHP_LAYOUT_DENSE || b->layout == RHP_LAYOUT_DENSE_RM;
-  if (dense && (b->mode == RHP_MODE_HTTP ? b->layout != RHP_LAYOUT_DENSE || (b->flags & RHP_BATCH_SPECULATIVE) : false))
-    return -22;   /* http mode: header-major dense records, not speculative */
+  const bool compact = b->layout == RHP_LAYOUT_COMPACT, dense = rhp_layout_dense(b->layout);
   Params prm = batch_params(b);
   prm.last_len = b->last_len;
   prm.compact = !(b->flags & RHP_BATCH_SPECULATIVE);
   prm.wt_records = b->mode == RHP_MODE_PHR && b->layout != RHP_LAYOUT_REQUEST_MAJOR && b->layout != RHP_LAYOUT_DENSE_RM;
-  if (dense) {   /* 8-byte request records and u16 lengths (header-major), the wide ones behind them */
-    prm.dreq = reinterpret_cast<uint2 *>(b->reqs);
-    prm.reqs = reinterpret_cast<rhp_req_t *>(reinterpret_cast<uint8_t *>(b->reqs) + RHP_DENSE_REQ_WIDE_OFF(b->n));
-    prm.lens16 = reinterpret_cast<uint16_t *>(b->hdrs);
-    prm.ovf32 = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(b->hdrs) + RHP_DENSE_OVF_OFF(b->n, b->max_headers));
-    prm.hdrs = reinterpret_cast<rhp_hdr_t *>(reinterpret_cast<uint8_t *>(b->hdrs) + RHP_DENSE_WIDE_OFF(b->n, b->max_headers));
-    prm.hs_req = b->max_headers;   /* the exact path's wide records: request-major */
-    prm.hs_hdr = 1u;
-    const bool rm = b->layout == RHP_LAYOUT_DENSE_RM;   /* the u16 lengths request-major or header-major */
-    prm.rec_req = rm ? b->max_headers : 1u;
-    prm.rec_hdr = rm ? 1u : b->n;
-    if (b->mode == RHP_MODE_HTTP) {   /* the compact http records, as RHP_LAYOUT_COMPACT's */
-      prm.hc = reinterpret_cast<uint2 *>(b->http);
-      prm.http = reinterpret_cast<rhp_http_t *>(reinterpret_cast<uint8_t *>(b->http) + RHP_COMPACT_HTTP_WIDE_OFF(b->n));
-    }
-  }
-  if (compact) {   /* lengths header-major at hdrs, the wide records request-major behind them */
-    prm.lens = reinterpret_cast<uint32_t *>(b->hdrs);
-    prm.hdrs = reinterpret_cast<rhp_hdr_t *>(reinterpret_cast<uint8_t *>(b->hdrs) + RHP_COMPACT_WIDE_OFF(b->n, b->max_headers));
-    prm.rec_req = 1u;
-    prm.rec_hdr = b->n;
-    if (b->mode == RHP_MODE_HTTP) {   /* 8-byte http records, the wide ones (and the replay's hints) behind them */
-      prm.hc = reinterpret_cast<uint2 *>(b->http);
-      prm.http = reinterpret_cast<rhp_http_t *>(reinterpret_cast<uint8_t *>(b->http) + RHP_COMPACT_HTTP_WIDE_OFF(b->n));
-    }
-  }
 
   /* the DFA kernel addresses windows with u32 offsets from its workgroup's
    * range start; a range of ~4 GiB runs the exact path inside it */
@@ -2612,9 +2567,10 @@ int rhp_fixup_sessions(const rhp_batch_t *b, const rhp_session_t *sessions, uint
 {
   if (!b || (n_sessions && (!sessions || !results || !req_start))) return -22;
   if (n_sessions == 0) return 0;
-  if (b->mode != RHP_MODE_HTTP || !(b->flags & RHP_BATCH_SPECULATIVE)) return -22;
+  /* the batch rhp_parse_batch took, speculative: so http mode, rhp_hdr_t records */
+  if (rhp_batch_check(b, 1) < 0 || !(b->flags & RHP_BATCH_SPECULATIVE)) return -22;
+  /* an empty batch's sessions are walked too (rhp_batch_check asks no pointers of it) */
   if (!b->bytes_rw || !b->offsets || !b->reqs || !b->http || (b->max_headers && !b->hdrs)) return -22;
-  if (b->layout != RHP_LAYOUT_REQUEST_MAJOR && b->layout != RHP_LAYOUT_HEADER_MAJOR) return -22;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Params prm = batch_params(b);
   prm.compact = true;

@@ -289,3 +289,86 @@ def test_emulator_chunked_paths_vs_oracle():
     reqs, hdrs, http, rw = run_oracle(buf, off, 16, rhp.MODE_HTTP)
     assert_same(canon(res, rhp.MODE_HTTP), to_rhp(reqs, hdrs, http, rhp.MODE_HTTP), buf, off, "emulated chunked paths")
     assert np.array_equal(res.bytes_out, rw)
+
+
+# ---------------------------------------------------------------------------
+# What rhp_parse_batch refuses (include/rhp_records.h rhp_batch_check): the
+# expected column is written out by hand from rhp_parse_batch's rules (rhp.h:
+# compact and dense records not with RHP_BATCH_SPECULATIVE, the flag in http
+# mode only, RHP_LAYOUT_DENSE_RM in phr mode only, max_headers <= 64,
+# n * max_headers < 2^32, last_len in phr mode only), not computed.  n = 1 and
+# one 64-byte request, so a case that is wrongly accepted parses nothing else.
+
+_P, _H = rhp.MODE_PHR, rhp.MODE_HTTP
+_R, _HM, _C, _D, _DRM = (rhp.LAYOUT_REQUEST_MAJOR, rhp.LAYOUT_HEADER_MAJOR, rhp.LAYOUT_COMPACT, rhp.LAYOUT_DENSE,
+                         rhp.LAYOUT_DENSE_RM)
+_S = 1   # RHP_BATCH_SPECULATIVE
+# (id, mode, layout, flags, max_headers, n, last_len given, expected)
+REFUSALS = [
+    ("phr-request-major", _P, _R, 0, 16, 1, False, 0),
+    ("phr-header-major", _P, _HM, 0, 16, 1, False, 0),
+    ("phr-compact", _P, _C, 0, 16, 1, False, 0),
+    ("phr-dense", _P, _D, 0, 16, 1, False, 0),
+    ("phr-dense-rm", _P, _DRM, 0, 16, 1, False, 0),
+    ("http-request-major", _H, _R, 0, 16, 1, False, 0),
+    ("http-header-major", _H, _HM, 0, 16, 1, False, 0),
+    ("http-compact", _H, _C, 0, 16, 1, False, 0),
+    ("http-dense", _H, _D, 0, 16, 1, False, 0),
+    ("http-dense-rm", _H, _DRM, 0, 16, 1, False, -22),
+    ("phr-speculative-request-major", _P, _R, _S, 16, 1, False, -22),
+    ("phr-speculative-compact", _P, _C, _S, 16, 1, False, -22),
+    ("phr-speculative-dense", _P, _D, _S, 16, 1, False, -22),
+    ("http-speculative-request-major", _H, _R, _S, 16, 1, False, 0),
+    ("http-speculative-header-major", _H, _HM, _S, 16, 1, False, 0),
+    ("http-speculative-compact", _H, _C, _S, 16, 1, False, -22),
+    ("http-speculative-dense", _H, _D, _S, 16, 1, False, -22),
+    ("http-speculative-dense-rm", _H, _DRM, _S, 16, 1, False, -22),
+    ("max-headers-64", _P, _R, 0, 64, 1, False, 0),
+    ("max-headers-65", _P, _R, 0, 65, 1, False, -22),
+    ("records-past-2^32", _P, _R, 0, 64, 1 << 26, False, -22),
+    ("phr-last-len", _P, _R, 0, 16, 1, True, 0),
+    ("http-last-len", _H, _R, 0, 16, 1, True, -22),
+    ("unknown-layout", _P, 5, 0, 16, 1, False, -22),
+    ("unknown-flag", _H, _R, 2, 16, 1, False, -22),
+    ("unknown-mode", 2, _R, 0, 16, 1, False, -22),
+]
+REFUSAL_REQUEST = b"GET /" + b"p" * 31 + b" HTTP/1.1\r\nHost: refusal\r\n\r\n"
+assert len(REFUSAL_REQUEST) == 64
+
+
+@pytest.mark.parametrize("case", REFUSALS, ids=[c[0] for c in REFUSALS])
+def test_host_parsers_refuse_what_parse_batch_refuses(case):
+    _, mode, layout, flags, maxh, n, with_last_len, want = case
+    buf = np.frombuffer(REFUSAL_REQUEST + bytes(rhp.RHP_PAD), dtype=np.uint8).copy()
+    off = np.array([0, 64], dtype=np.uint64)
+    last_len = np.zeros(1, dtype=np.uint64)
+    for parse in (lambda b: rhp.host().rhp_cpu_parse_batch(ctypes.byref(b)),
+                  lambda b: rhp.host().rhp_emu_parse_batch(ctypes.byref(b), None)):
+        rw, reqs, hdrs, http = buf.copy(), *(np.zeros(1 << 16, dtype=np.uint8) for _ in range(3))
+        b = rhp.Batch(rw.ctypes.data, rw.ctypes.data, off.ctypes.data, rw.size, n, maxh, mode, layout, reqs.ctypes.data,
+                      hdrs.ctypes.data, http.ctypes.data, None, flags, 0, last_len.ctypes.data if with_last_len else None)
+        assert parse(b) == want
+
+
+@pytest.mark.gpu
+def test_gpu_parse_batch_refusals():
+    """rhp_parse_batch itself against the same hand-written column: every
+    refused case, and one accepted case per layout (n = 1); no result is read"""
+    import torch
+    dev = "cuda"
+    buf = torch.from_numpy(np.frombuffer(REFUSAL_REQUEST + bytes(rhp.RHP_PAD), dtype=np.uint8).copy()).to(dev)
+    off = torch.tensor([0, 64], dtype=torch.int64, device=dev)
+    last_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    reqs, hdrs, http = (torch.zeros(1 << 16, dtype=torch.uint8, device=dev) for _ in range(3))
+    accepted = {"phr-request-major", "phr-header-major", "phr-compact", "phr-dense", "phr-dense-rm"}
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    got = {}
+    for name, mode, layout, flags, maxh, n, with_last_len, want in REFUSALS:
+        if want == 0 and name not in accepted:
+            continue
+        b = rhp.Batch(buf.data_ptr(), buf.data_ptr(), off.data_ptr(), buf.numel(), n, maxh, mode, layout, reqs.data_ptr(),
+                      hdrs.data_ptr(), http.data_ptr(), None, flags, 0, last_len.data_ptr() if with_last_len else None)
+        got[name] = (rhp.lib().rhp_parse_batch(ctypes.byref(b), stream), want)
+    torch.cuda.synchronize()
+    assert len(got) == len(accepted) + sum(1 for c in REFUSALS if c[-1] == -22)
+    assert not {k: v for k, v in got.items() if v[0] != v[1]}
