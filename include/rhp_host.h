@@ -9,6 +9,8 @@
  *                         "host" session parser use it
  *   rhp_emu_parse_batch   CPU emulation of the kernel's DFA algorithm, block for
  *                         block (tests only); stats[3] = fast ok, fast -1, exact
+ *   rhp_emu_fixup_sessions  rhp_fixup_kernel's prefix and walk per session, on
+ *                         the host (tests only)
  *   (both take an rhp_batch_t (include/rhp.h) whose pointers are host memory,
  *   of any alignment, and refuse with -22 what rhp_parse_batch refuses:
  *   rhp_records.h rhp_batch_check)
@@ -46,6 +48,12 @@ int rhp_cpu_parse_batch(const rhp_batch_t *batch);
 int rhp_cpu_fixup_sessions(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
                            rhp_session_result_t *results, uint64_t *req_start);
 int rhp_emu_parse_batch(const rhp_batch_t *batch, uint64_t *stats);
+/* rhp_cpu_fixup_sessions as the device runs it (tests only): per session the
+ * kernel's prefix of whole pieces, 64 per step (rhp_scalar.h fixup_lane_other,
+ * fixup_step_stop: the code rhp_fixup_kernel runs), then the walk from the
+ * first other piece.  The same outputs as rhp_cpu_fixup_sessions. */
+int rhp_emu_fixup_sessions(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
+                           rhp_session_result_t *results, uint64_t *req_start);
 /* rhp_pack_dense (rhp.h) on the host, over host copies of the batch's records
  * (the reactor's host-async parser exercises the dense copy-back with it) */
 int rhp_cpu_pack_dense(const rhp_batch_t *batch, rhp_req_dense_t *dreq, rhp_http_compact_t *hc, uint16_t *lens16);
@@ -114,6 +122,10 @@ int rhp_http_read_cpu(uint8_t *buf, size_t len, rhp_http_req_t *req, rhp_phr_hea
 int rhp_test_chunk_window(const uint8_t *line, uint32_t nw, uint64_t avail, int64_t *res, uint64_t *data_off,
                           uint64_t *data_len);
 int64_t rhp_test_chunk_exact(const uint8_t *body, uint64_t at, uint64_t size, uint64_t *data_off, uint64_t *data_len);
+/* Test hook (tests/test_sessions.py): whole[j] = 1 where piece j of a parsed
+ * speculative batch is one the fix-up's prefix takes (rhp_scalar.h
+ * fixup_piece_whole), else 0; 0 or -22 */
+int rhp_test_fixup_whole(const rhp_batch_t *batch, uint8_t *whole);
 
 #ifdef __cplusplus
 }

@@ -69,7 +69,7 @@ RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_versio
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
-                "rhp_cpu_classify_batch", "rhp_test_chunk_window",
+                "rhp_cpu_classify_batch", "rhp_emu_fixup_sessions", "rhp_test_fixup_whole", "rhp_test_chunk_window",
                 "rhp_test_chunk_exact")
 
 _rhp = None
@@ -196,6 +196,10 @@ def host() -> ctypes.CDLL:
         _host.rhp_http_read_cpu.restype = ctypes.c_int
         _host.rhp_cpu_fixup_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp]
         _host.rhp_cpu_fixup_sessions.restype = ctypes.c_int
+        _host.rhp_emu_fixup_sessions.argtypes = _host.rhp_cpu_fixup_sessions.argtypes
+        _host.rhp_emu_fixup_sessions.restype = ctypes.c_int
+        _host.rhp_test_fixup_whole.argtypes = [ctypes.POINTER(Batch), vp]
+        _host.rhp_test_fixup_whole.restype = ctypes.c_int
         _host.rhp_expand_records.argtypes = [ctypes.POINTER(Batch), vp, vp, vp]
         _host.rhp_expand_records.restype = ctypes.c_int
         _host.rhp_expand_http.argtypes = [ctypes.POINTER(Batch), vp, vp, vp]
@@ -706,9 +710,9 @@ def pack_sessions(sessions, split=True):
     return buf, off, ss, np.array(starts, dtype=np.uint64)
 
 
-def fixup_cpu(buf, off, sessions, max_headers: int = 16, emulate_dfa: bool = False, layout: int = LAYOUT_REQUEST_MAJOR):
-    """Speculative http batch (host exact parser, or the kernel's DFA emulation)
-    + rhp_cpu_fixup_sessions.  Returns (Result, session results, req_start)."""
+def speculative_cpu(buf, off, max_headers: int = 16, emulate_dfa: bool = False, layout: int = LAYOUT_REQUEST_MAJOR):
+    """The speculative http batch of the pieces on the host (the exact parser,
+    or the kernel's DFA emulation): (Batch, Result over the same records)."""
     b, res = _host_batch(buf, off, max_headers, MODE_HTTP, layout, None, BATCH_SPECULATIVE)
     if emulate_dfa:
         rc = host().rhp_emu_parse_batch(ctypes.byref(b), None)
@@ -716,16 +720,46 @@ def fixup_cpu(buf, off, sessions, max_headers: int = 16, emulate_dfa: bool = Fal
         rc = host().rhp_cpu_parse_batch(ctypes.byref(b))
     if rc != 0:
         raise RuntimeError(f"host parse failed: {rc}")
-    out = np.zeros(len(sessions), dtype=SESSION_RESULT_DTYPE)
-    starts = np.zeros(max(len(off) - 1, 1), dtype=np.uint64)
-    rc = host().rhp_cpu_fixup_sessions(ctypes.byref(b), _ptr(sessions), len(sessions), _ptr(out), _ptr(starts))
+    return b, res
+
+
+def whole_pieces(b) -> np.ndarray:
+    """bool [n]: the pieces of speculative_cpu's batch that the fix-up's prefix
+    takes as they are (rhp_scalar.h fixup_piece_whole, the kernel's predicate)."""
+    whole = np.zeros(max(b.n, 1), dtype=np.uint8)
+    rc = host().rhp_test_fixup_whole(ctypes.byref(b), _ptr(whole))
     if rc != 0:
-        raise RuntimeError(f"rhp_cpu_fixup_sessions failed: {rc}")
-    return _host_done(res, len(off) - 1, max_headers, layout), out, starts
+        raise RuntimeError(f"rhp_test_fixup_whole failed: {rc}")
+    return whole[: b.n].astype(bool)
 
 
-def fixup_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_DFA, layout: int = LAYOUT_REQUEST_MAJOR):
-    """Speculative http batch on the GPU + rhp_fixup_sessions, one stream."""
+def fixup_host(b, res, sessions, prefix: bool = False):
+    """rhp_cpu_fixup_sessions, or with `prefix` rhp_emu_fixup_sessions (the
+    kernel's prefix of whole pieces, then the walk), over the records of
+    speculative_cpu.  Returns (Result, session results, req_start)."""
+    fn = host().rhp_emu_fixup_sessions if prefix else host().rhp_cpu_fixup_sessions
+    out = np.zeros(len(sessions), dtype=SESSION_RESULT_DTYPE)
+    starts = np.zeros(max(b.n, 1), dtype=np.uint64)
+    rc = fn(ctypes.byref(b), _ptr(sessions), len(sessions), _ptr(out), _ptr(starts))
+    if rc != 0:
+        raise RuntimeError(f"host session fix-up failed: {rc}")
+    return _host_done(res, b.n, b.max_headers, b.layout), out, starts
+
+
+def fixup_cpu(buf, off, sessions, max_headers: int = 16, emulate_dfa: bool = False, layout: int = LAYOUT_REQUEST_MAJOR,
+              prefix: bool = False):
+    """Speculative http batch (host exact parser, or the kernel's DFA emulation)
+    + rhp_cpu_fixup_sessions (prefix: rhp_emu_fixup_sessions, the host twin of
+    the kernel's wave-parallel prefix).  Returns (Result, session results, req_start)."""
+    b, res = speculative_cpu(buf, off, max_headers, emulate_dfa, layout)
+    return fixup_host(b, res, sessions, prefix)
+
+
+def fixup_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_DFA, layout: int = LAYOUT_REQUEST_MAJOR,
+              with_batch: bool = False):
+    """Speculative http batch on the GPU + rhp_fixup_sessions, one stream.
+    with_batch: the DeviceBatch too, as a fourth value (its device records are
+    what the fix-up left: rhp_pack_dense can run over them)."""
     import torch
     lib().rhp_set_impl(impl)
     try:
@@ -741,7 +775,8 @@ def fixup_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_DFA, l
         if rc != 0:
             raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
         res = db.result()
-        return res, dres.cpu().numpy().view(SESSION_RESULT_DTYPE), dst.cpu().numpy().view(np.uint64)
+        out = res, dres.cpu().numpy().view(SESSION_RESULT_DTYPE), dst.cpu().numpy().view(np.uint64)
+        return out + (db,) if with_batch else out
     finally:
         lib().rhp_set_impl(IMPL_DFA)
 

@@ -210,6 +210,45 @@ extern "C" int rhp_emu_parse_batch(const rhp_batch_t *b, uint64_t *stats /* [3] 
   return 0;
 }
 
+/* test hook: rhp_fixup_kernel's work per session on the host (as
+ * rhp_cpu_fixup_sessions, which walks every session from its first piece):
+ * the prefix of whole pieces taken kFixupStep per step by the kernel's own
+ * predicate and stop rule (rhp_scalar.h), the lanes of a step in a loop, then
+ * the walk from the first other piece. */
+extern "C" int rhp_emu_fixup_sessions(const rhp_batch_t *b, const rhp_session_t *sessions, uint32_t n_sessions,
+                                      rhp_session_result_t *results, uint64_t *req_start)
+{
+  if (!b || b->mode != RHP_MODE_HTTP || !(b->flags & RHP_BATCH_SPECULATIVE)) return -22;
+  const rhp_view_t v = rhp_batch_view(b);
+  const FixupIO io{b->bytes_rw, b->offsets, v.reqs, v.hdrs, v.http, v.hs_req, v.hs_hdr, b->max_headers};
+  for (uint32_t k = 0; k < n_sessions; k++) {
+    const rhp_session_t ss = sessions[k];
+    uint32_t from = ss.piece_lo;
+    while (from < ss.piece_hi) {
+      uint64_t a[kFixupStep], other = 0;
+      for (uint32_t lane = 0; lane < kFixupStep; lane++)
+        other |= (uint64_t) fixup_lane_other(io.http, io.off, from + lane, ss.piece_hi, &a[lane]) << lane;
+      const uint32_t stop = fixup_step_stop(from, ss.piece_hi, other);
+      for (uint32_t lane = 0; lane < kFixupStep && from + lane < stop; lane++) req_start[from + lane] = a[lane];
+      from = stop;
+      if (other) break;
+    }
+    fixup_session_t(io, ss.piece_lo, ss.piece_hi, req_start, &results[k],
+                    [&](uint64_t at) { return PlainBytes{b->bytes_rw + at}; }, PlainDechunk(), from);
+  }
+  return 0;
+}
+
+/* test hook: fixup_piece_whole (rhp_scalar.h) of every piece of a parsed
+ * speculative batch, whole[j] = 0 / 1 */
+extern "C" int rhp_test_fixup_whole(const rhp_batch_t *b, uint8_t *whole)
+{
+  if (!b || b->mode != RHP_MODE_HTTP || !(b->flags & RHP_BATCH_SPECULATIVE)) return -22;
+  const rhp_view_t v = rhp_batch_view(b);
+  for (uint32_t j = 0; j < b->n; j++) whole[j] = fixup_piece_whole(v.http[j], b->offsets[j + 1] - b->offsets[j]) ? 1 : 0;
+  return 0;
+}
+
 /* test hook: one_chunk_window over the nw (<= 32) bytes at `line`
  * (tests/test_cpu_units.py compares it with one_chunk_t); returns 0 when the
  * window cannot decide */

@@ -2372,17 +2372,12 @@ __global__ __launch_bounds__(256) void rhp_fixup_kernel(Params p, const rhp_sess
   if (k >= n_sessions) return;   /* wave-uniform */
   const rhp_session_t ss = sessions[k];
   uint32_t from = ss.piece_lo;
-  while (from < ss.piece_hi) {
+  static_assert(kFixupStep == 64, "a step of the prefix is one wave");
+  while (from < ss.piece_hi) {   /* rhp_scalar.h: the prefix, a step per iteration */
     const uint32_t j = from + lane;
-    bool whole = false;
-    uint64_t a = 0;
-    if (j < ss.piece_hi) {
-      const rhp_http_t x = p.http[j];
-      a = p.offsets[j];
-      whole = x.result == 1 && x.body_kind != RHP_BODY_CHUNKED_PENDING && x.consumed == p.offsets[j + 1] - a;
-    }
-    const uint64_t other = __builtin_amdgcn_ballot_w64(!whole && j < ss.piece_hi);
-    const uint32_t stop = other ? from + (uint32_t) __builtin_ctzll(other) : min(from + 64u, ss.piece_hi);
+    uint64_t a;
+    const uint64_t other = __builtin_amdgcn_ballot_w64(fixup_lane_other(p.http, p.offsets, j, ss.piece_hi, &a));
+    const uint32_t stop = fixup_step_stop(from, ss.piece_hi, other);
     if (j < stop) req_start[j] = a;
     from = stop;
     if (other) break;

@@ -680,6 +680,40 @@ RHP_HD void fixup_session_t(const FixupIO &io, uint32_t p_lo, uint32_t p_hi, uin
   out->consumed = pos - b_lo;
 }
 
+/* The prefix of a session that needs no walk: its leading "whole" pieces, those
+ * whose speculative record is a request that ended exactly at the piece's end
+ * with no chunked body to de-frame.  fixup_session_t would take each of them
+ * as it is, in its own slot, so only req_start is written for them and the
+ * walk starts at the first other piece (p_from).  They are found
+ * kFixupStep pieces per step, lane l of a step looking at piece from + l:
+ * rhp_fixup_kernel runs the lanes as a wave and gathers fixup_lane_other
+ * with one ballot, rhp_emu_fixup_sessions (the host twin, tests) with a loop. */
+constexpr uint32_t kFixupStep = 64;
+
+RHP_HD bool fixup_piece_whole(const rhp_http_t &x, uint64_t plen)
+{
+  return x.result == 1 && x.body_kind != RHP_BODY_CHUNKED_PENDING && x.consumed == plen;
+}
+
+/* one lane of a step: piece j = from + lane; true when j is a piece of the
+ * session and not whole (the prefix ends there); *at = where piece j starts */
+RHP_HD bool fixup_lane_other(const rhp_http_t *http, const uint64_t *off, uint32_t j, uint32_t p_hi, uint64_t *at)
+{
+  *at = 0;
+  if (j >= p_hi) return false;
+  *at = off[j];
+  return !fixup_piece_whole(http[j], off[j + 1] - *at);
+}
+
+/* where a step from `from` stops, `other` being its lanes' fixup_lane_other
+ * (bit l: lane l): lanes below the stop write req_start, the next step starts
+ * there, and a step with `other` set is the last */
+RHP_HD uint32_t fixup_step_stop(uint32_t from, uint32_t p_hi, uint64_t other)
+{
+  if (other) return from + (uint32_t) __builtin_ctzll(other);
+  return p_hi - from < kFixupStep ? p_hi : from + kFixupStep;
+}
+
 }  // namespace rhp
 
 #endif

@@ -396,8 +396,6 @@ def test_pack_dense_cpu_fixup_chunked_stays_wide():
 def test_gpu_pack_dense_equals_cpu_pack(case):
     """rhp_pack_dense on the device's records, byte for byte the CPU pack of
     the same records (their parity with the oracle is the other tests')"""
-    import ctypes
-    import torch
     if case == "golden":
         spec, buf, off, _ = golden([s for s in HTTP_SETS if "chunked" not in s][0])
         maxh = spec["max_headers"]
@@ -411,6 +409,18 @@ def test_gpu_pack_dense_equals_cpu_pack(case):
     n = len(off) - 1
     db = rhp.DeviceBatch(buf, off, maxh, rhp.MODE_HTTP, layout=rhp.LAYOUT_REQUEST_MAJOR)
     db.launch()
+    _, _, _, dense = gpu_pack_equals_cpu_pack(db, n, maxh)
+    assert dense > 0 if case != "chunked" else dense == 0   # (de-framed chunked bodies: all wide)
+    if case == "limits":
+        assert 0 < dense < n   # (all wide would compare nothing)
+
+
+def gpu_pack_equals_cpu_pack(db, n, maxh):
+    """rhp_pack_dense over the device records of `db` as they are now, compared
+    with the CPU pack of the same records fetched; (Result, dreq [n, 8], hc
+    [n, 8], how many requests check_pack found dense)"""
+    import ctypes
+    import torch
     dd = torch.zeros(8 * n, dtype=torch.uint8, device="cuda")
     dh = torch.zeros(8 * n, dtype=torch.uint8, device="cuda")
     dl = torch.zeros(max(maxh * n, 1), dtype=torch.int16, device="cuda")
@@ -427,7 +437,35 @@ def test_gpu_pack_dense_equals_cpu_pack(case):
     nh = np.where((want_d.reshape(n, 8)[:, 7] & rhp.DENSE_WIDE) == 0, want_d.reshape(n, 8)[:, 5], 0)
     used = np.arange(maxh)[:, None] < nh[None, :]
     assert (got_l.reshape(maxh, n)[used] == want_l.reshape(maxh, n)[used]).all()
-    dense = check_pack(res, n, maxh)
-    assert dense > 0 if case != "chunked" else dense == 0   # (de-framed chunked bodies: all wide)
-    if case == "limits":
-        assert 0 < dense < n   # (all wide would compare nothing)
+    return res, want_d.reshape(n, 8), want_h.reshape(n, 8), check_pack(res, n, maxh)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["shapes", "mixed"])
+def test_gpu_fixup_then_pack_dense(case):
+    """a reactor round on the device: speculative parse, rhp_fixup_sessions,
+    rhp_pack_dense over the records the fix-up left.  The fix-up's answers are
+    the reference loop's; the packed copies are the CPU pack of those records;
+    a chunked body de-framed by the fix-up keeps its slot wide in both."""
+    import session_sets
+    import test_sessions
+    if case == "shapes":
+        buf, off, sess = session_sets.packed_shapes()
+        want = test_sessions.shapes_oracle()
+    else:
+        buf, off, sess, _ = rhp.pack_sessions(test_sessions.make_sessions(200, 9))
+        want = test_sessions.oracle_sessions(buf, off, [(int(a), int(b)) for a, b in sess])
+    n = len(off) - 1
+    _, results, starts, db = rhp.fixup_gpu(buf, off, sess, 16, with_batch=True)
+    res, dreq, hc, dense = gpu_pack_equals_cpu_pack(db, n, 16)
+    test_sessions.check(res, results, starts, buf, off, sess, f"gpu fix-up then pack {case}", want=want)
+    used = test_sessions.used_slots(sess, results)
+    assert 0 < dense < n
+    assert 0 < int(((dreq[used, 7] & rhp.DENSE_WIDE) == 0).sum()) < len(used)
+    # the slots whose chunked body the fix-up de-framed: the oracle's requests with
+    # Transfer-Encoding set, in session order
+    chunked = [int(lo) + m for (lo, _), seq in zip(sess, want[0]) for m, q in enumerate(seq)
+               if q[0] == 1 and any(name.upper() == b"TRANSFER-ENCODING" and value for name, value in q[5])]
+    assert len(chunked) > 10
+    assert (res.http["body_kind"][chunked] == 1).all()
+    assert (dreq[chunked, 7] & rhp.DENSE_WIDE).all() and (hc[chunked, 2] & rhp.HTTP_WIDE).all()
