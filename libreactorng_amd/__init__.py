@@ -482,12 +482,74 @@ def parse_cpu_exact(buf: np.ndarray, off: np.ndarray, max_headers: int = 16, mod
     return _host_done(res, len(off) - 1, max_headers, layout)
 
 
+GUARD_BYTE, GUARD_BYTE_ALT = 0xA5, 0x3C   # the guard pattern; the second where the fill is the first
+
+
+class GuardError(AssertionError):
+    """a guard byte beside a buffer no longer holds the pattern"""
+
+
+def check_guard_bytes(name: str, before: np.ndarray, after: np.ndarray, pattern: int) -> None:
+    """Raise GuardError if a byte of `before` (the bytes that end where the
+    buffer starts) or `after` (the bytes that start where it ends) is not
+    `pattern`: the buffer, the side and the first offset, counted from the
+    buffer's start (negative) or from its end."""
+    for side, g, base in (("before", before, -len(before)), ("after", after, 0)):
+        bad = np.flatnonzero(np.asarray(g) != pattern)
+        if len(bad):
+            raise GuardError(f"{name}: {len(bad)} guard bytes {side} the buffer overwritten, first at offset "
+                             f"{base + int(bad[0])} from its {'start' if side == 'before' else 'end'} "
+                             f"(holds 0x{int(g[bad[0]]):02x}, pattern 0x{pattern:02x})")
+
+
+class Guarded:
+    """`size` bytes (tests: a device buffer the library writes) as a slice of a
+    larger allocation: `guard` bytes of a pattern directly before and after
+    it, `shift` more bytes of the pattern before it.  The slice starts at the
+    allocation's base plus a multiple of ALIGN (the alignment of a torch
+    allocation) plus `shift`.  fill: the byte the slice holds at first (None:
+    zero); the pattern differs from it.  data: the slice's first bytes.
+    Without guard and shift the allocation is the plain one (torch.zeros)."""
+
+    ALIGN = 512
+
+    def __init__(self, name: str, size: int, guard: int = 0, fill: int | None = None, device: str = "cuda",
+                 shift: int = 0, data: np.ndarray | None = None):
+        import torch
+        self.name, self.size, self.guard = name, size, guard
+        self.pattern = GUARD_BYTE_ALT if fill == GUARD_BYTE else GUARD_BYTE
+        self.front = ((guard + self.ALIGN - 1) & ~(self.ALIGN - 1)) + shift
+        if self.front or guard:
+            self.buf = torch.full((self.front + size + guard,), self.pattern, dtype=torch.uint8, device=device)
+            self.view = self.buf[self.front: self.front + size]
+            self.view.fill_(fill or 0)
+        else:
+            self.buf = self.view = (torch.zeros(size, dtype=torch.uint8, device=device) if not fill
+                                    else torch.full((size,), fill, dtype=torch.uint8, device=device))
+        if data is not None:
+            self.view[: data.size].copy_(torch.from_numpy(np.ascontiguousarray(data).view(np.uint8).reshape(-1)))
+
+    def guards(self):
+        """(the bytes before the slice, the bytes after it) as host arrays: an ordinary copy"""
+        return self.buf[: self.front].cpu().numpy(), self.buf[self.front + self.size:].cpu().numpy()
+
+    def check(self) -> None:
+        check_guard_bytes(self.name, *self.guards(), self.pattern)
+
+
 class DeviceBatch:
-    """A batch resident in HBM plus its output buffers (torch tensors as plumbing)."""
+    """A batch resident in HBM plus its output buffers (torch tensors as plumbing).
+
+    fill (a byte, tests): reqs, hdrs and http hold it before the launch, not
+    zero (rhp.h asks no caller to zero them): a record the parser never wrote
+    reads back as the fill.  guard (bytes, tests): reqs, hdrs, http and bytes
+    are Guarded slices, with that many pattern bytes on both sides; result()
+    then calls check_guards().  bytes_shift (a multiple of 16, tests): bytes /
+    bytes_rw point that far into their allocation (rhp.h: 16-byte aligned)."""
 
     def __init__(self, buf: np.ndarray, off: np.ndarray, max_headers: int = 16, mode: int = MODE_PHR,
                  device: str = "cuda", layout: int = LAYOUT_REQUEST_MAJOR, last_len: np.ndarray | None = None,
-                 flags: int = 0):
+                 flags: int = 0, fill: int | None = None, guard: int = 0, bytes_shift: int = 0):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("no GPU visible: the rhp product path runs on MI355X only")
@@ -497,11 +559,23 @@ class DeviceBatch:
         self.layout = layout
         self.flags = flags
         self.host_buf, self.host_off = buf, off   # (references: result() describes the parsed batch over them)
-        self.bytes = torch.from_numpy(buf).to(device)
+        if bytes_shift < 0 or bytes_shift % 16:
+            raise ValueError("bytes_shift: a multiple of 16 (rhp.h: bytes is 16-byte aligned)")
+        self.fill, self.guard = fill, guard
+        self.guarded = {}   # name -> Guarded, the buffers check_guards() looks beside
+
+        def area(name, size, **kw):
+            g = self.guarded[name] = Guarded(name, size, guard, device=device, **kw)
+            return g.view
+
+        if guard or bytes_shift:
+            self.bytes = area("bytes", buf.size, shift=bytes_shift, data=buf)
+        else:
+            self.bytes = torch.from_numpy(buf).to(device)
         self.offsets = torch.from_numpy(off.view(np.int64)).to(device)
-        self.reqs = torch.zeros(max(reqs_bytes(self.n, layout), 8), dtype=torch.uint8, device=device)
-        self.hdrs = torch.zeros(max(hdrs_bytes(self.n, max_headers, layout), 8), dtype=torch.uint8, device=device)
-        self.http = torch.zeros(http_bytes(self.n, mode, layout), dtype=torch.uint8, device=device)
+        self.reqs = area("reqs", max(reqs_bytes(self.n, layout), 8), fill=fill)
+        self.hdrs = area("hdrs", max(hdrs_bytes(self.n, max_headers, layout), 8), fill=fill)
+        self.http = area("http", http_bytes(self.n, mode, layout), fill=fill)
         self.work = torch.zeros(RHP_WORK_WORDS, dtype=torch.int32, device=device)
         self.last_len = (torch.from_numpy(np.ascontiguousarray(last_len, dtype=np.uint64).view(np.int64)).to(device)
                          if last_len is not None else None)
@@ -511,6 +585,20 @@ class DeviceBatch:
                      self.n, self.max_headers, self.mode, self.layout, self.reqs.data_ptr(), self.hdrs.data_ptr(),
                      self.http.data_ptr(), self.work.data_ptr(), self.flags, 0,
                      self.last_len.data_ptr() if self.last_len is not None else None)
+
+    def fill_records(self, fill: int | None = None) -> None:
+        """reqs, hdrs and http filled again (default: with the batch's fill byte), on the current stream"""
+        v = self.fill or 0 if fill is None else fill
+        for t in (self.reqs, self.hdrs, self.http):
+            t.fill_(v)
+
+    def check_guards(self) -> None:
+        """Read the guards back (after a synchronize, ordinary copies); GuardError
+        names the buffer, the side and the first offset."""
+        import torch
+        torch.cuda.synchronize()
+        for g in self.guarded.values():
+            g.check()
 
     _runtime_checked = False   # one /proc/self/maps scan per process (it costs ~0.2 ms: not per launch)
 
@@ -528,6 +616,8 @@ class DeviceBatch:
     def result(self) -> Result:
         import torch
         torch.cuda.synchronize()
+        if self.guard:
+            self.check_guards()
         raw_reqs = self.reqs.cpu().numpy()
         reqs = expand_reqs(raw_reqs, self.n, self.layout)
         raw = self.hdrs.cpu().numpy()
@@ -580,11 +670,13 @@ class DeviceBatch:
 
 
 def parse_batch(buf: np.ndarray, off: np.ndarray, max_headers: int = 16, mode: int = MODE_PHR,
-                impl: int = IMPL_DFA, layout: int = LAYOUT_REQUEST_MAJOR, last_len: np.ndarray | None = None) -> Result:
-    """Parse a host batch on the GPU (copies in, one launch, copies out)."""
+                impl: int = IMPL_DFA, layout: int = LAYOUT_REQUEST_MAJOR, last_len: np.ndarray | None = None,
+                **device_batch) -> Result:
+    """Parse a host batch on the GPU (copies in, one launch, copies out).
+    device_batch: DeviceBatch's fill / guard / bytes_shift (tests)."""
     lib().rhp_set_impl(impl)
     try:
-        db = DeviceBatch(buf, off, max_headers, mode, layout=layout, last_len=last_len)
+        db = DeviceBatch(buf, off, max_headers, mode, layout=layout, last_len=last_len, **device_batch)
         db.launch()
         return db.result()
     finally:
@@ -756,18 +848,21 @@ def fixup_cpu(buf, off, sessions, max_headers: int = 16, emulate_dfa: bool = Fal
 
 
 def fixup_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_DFA, layout: int = LAYOUT_REQUEST_MAJOR,
-              with_batch: bool = False):
+              with_batch: bool = False, guard: int = 0):
     """Speculative http batch on the GPU + rhp_fixup_sessions, one stream.
     with_batch: the DeviceBatch too, as a fourth value (its device records are
-    what the fix-up left: rhp_pack_dense can run over them)."""
+    what the fix-up left: rhp_pack_dense can run over them).  guard (bytes,
+    tests): the batch's buffers and the fix-up's two outputs are Guarded, and
+    checked once both kernels have run."""
     import torch
     lib().rhp_set_impl(impl)
     try:
-        db = DeviceBatch(buf, off, max_headers, MODE_HTTP, layout=layout, flags=BATCH_SPECULATIVE)
+        db = DeviceBatch(buf, off, max_headers, MODE_HTTP, layout=layout, flags=BATCH_SPECULATIVE, guard=guard)
         db.launch()
         ds = torch.from_numpy(sessions.view(np.uint8).copy()).to("cuda")
-        dres = torch.zeros(len(sessions) * SESSION_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-        dst = torch.zeros(max(db.n, 1) * 8, dtype=torch.uint8, device="cuda")
+        gres = Guarded("results", len(sessions) * SESSION_RESULT_DTYPE.itemsize, guard)
+        gst = Guarded("req_start", max(db.n, 1) * 8, guard)
+        dres, dst = gres.view, gst.view
         d = db.desc()
         rc = lib().rhp_fixup_sessions(ctypes.byref(d), ctypes.c_void_p(ds.data_ptr()), len(sessions),
                                       ctypes.c_void_p(dres.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
@@ -775,6 +870,9 @@ def fixup_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_DFA, l
         if rc != 0:
             raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
         res = db.result()
+        if guard:
+            gres.check()
+            gst.check()
         out = res, dres.cpu().numpy().view(SESSION_RESULT_DTYPE), dst.cpu().numpy().view(np.uint64)
         return out + (db,) if with_batch else out
     finally:

@@ -131,6 +131,7 @@ enum : uint32_t {
   kPark = 0,                                     /* the DONE index: idle lanes step here */
   kDeferExact = 0x8000u,                         /* reqs[i].flags while deferred (kernel-internal) */
   kDeferDense = 0x80u,                           /* ... rhp_req_dense_t flags (RHP_LAYOUT_DENSE) */
+  kDeferHc = 0x8000u,                            /* rhp_http_compact_t flags while deferred (kernel-internal) */
   /* http mode: the replay's instructions, in the body_kind word of the hint
    * finalize leaves in http[i] (ret in the low 16 bits) */
   kHintExact = 0x40000000u,
@@ -1308,6 +1309,11 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
     *wg_deferred = 1u;
     const uint32_t at = atomicAdd(defer_n, 1u);
     if (at < kDeferCap) defer_list[at] = (uint16_t) (i - wg_lo);
+    /* compact http records: the hint goes to the request's wide record, and
+     * only a deferred request's wide record is written at all (any other one
+     * holds the caller's bytes), so the compact record says which ones are
+     * hints when the replay scans the range; the replay overwrites it */
+    if constexpr (HTTP && COMPACT) store_hc(p, i, (uint32_t) kDeferHc << 16, 0u);
   };
 
   /* ---- decode ----
@@ -2269,6 +2275,9 @@ __global__ __launch_bounds__(WAVES * 64, RHP_WAVES_PER_SIMD) void rhp_dfa_kernel
         if (direct) {   /* the range in order: what the first pass would have done */
           i = wg_lo + k;
           h = head(i);
+          /* compact records: a hint only where the loop marked the request deferred */
+          if constexpr (HTTP && COMPACT)
+            if (!((*GLOBAL(const uint32_t, &p.hc[i].x) >> 16) & kDeferHc)) h.hint = u32x4a4{0u, 0u, 0u, 0u};
           const uint32_t f = what(h);
           const int fr = !f                              ? kFrameDone
                          : (f & kHintExact)              ? kFrameSlow

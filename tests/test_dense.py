@@ -415,20 +415,23 @@ def test_gpu_pack_dense_equals_cpu_pack(case):
         assert 0 < dense < n   # (all wide would compare nothing)
 
 
-def gpu_pack_equals_cpu_pack(db, n, maxh):
+def gpu_pack_equals_cpu_pack(db, n, maxh, guard=0, fill=None):
     """rhp_pack_dense over the device records of `db` as they are now, compared
     with the CPU pack of the same records fetched; (Result, dreq [n, 8], hc
-    [n, 8], how many requests check_pack found dense)"""
+    [n, 8], how many requests check_pack found dense).  guard, fill: the three
+    outputs are rhp.Guarded slices that hold `fill` first, their guards checked."""
     import ctypes
     import torch
-    dd = torch.zeros(8 * n, dtype=torch.uint8, device="cuda")
-    dh = torch.zeros(8 * n, dtype=torch.uint8, device="cuda")
-    dl = torch.zeros(max(maxh * n, 1), dtype=torch.int16, device="cuda")
+    outs = [rhp.Guarded(name, size, guard, fill) for name, size in
+            (("dreq", 8 * n), ("hc", 8 * n), ("lens16", 2 * max(maxh * n, 1)))]
+    dd, dh, dl = (g.view for g in outs)
     d = db.desc()
     rc = rhp.lib().rhp_pack_dense(ctypes.byref(d), dd.data_ptr(), dh.data_ptr(), dl.data_ptr(),
                                   torch.cuda.current_stream().cuda_stream)
     assert rc == 0
     res = db.result()
+    for g in outs:
+        g.check()
     want_d, want_h, want_l = rhp.pack_dense_cpu(res, n, maxh)
     got_l = dl.cpu().numpy().view(np.uint16)[: maxh * n]
     assert (dd.cpu().numpy() == want_d).all()

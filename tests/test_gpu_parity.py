@@ -165,10 +165,12 @@ def test_gpu_chunked_paths_vs_oracle(shift, n):
 
 def test_gpu_repeated_launches_rearm_work_counter():
     buf, off = rhp.generate(rhp.GEN_ZIPF, 5000, 77)
+    """every relaunch into record buffers refilled with 0xFF: a stale buffer
+    would hold the launch before's (right) answers"""
     db = rhp.DeviceBatch(buf, off, 32)
     want = to_rhp(*run_oracle(buf, off, 32)[:3], rhp.MODE_PHR)
     for _ in range(5):
-        db.reqs.zero_()
+        db.fill_records(0xFF)
         db.launch()
         assert_same(canon(db.result(), rhp.MODE_PHR), want, buf, off, "relaunch")
 

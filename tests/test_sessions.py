@@ -505,12 +505,13 @@ def test_fixup_gpu_prefixes_header_major():
     gpu_prefixes(HM)
 
 
-def gpu_shapes(first, maxh, impl, layout):
+def gpu_shapes(first, maxh, impl, layout, guard=0):
     """the shapes set (or its first sessions) on the device: the reference loop's
-    answers, and record for record what the host twin of the kernel leaves"""
+    answers, and record for record what the host twin of the kernel leaves
+    (guard: rhp.fixup_gpu's, guards beside every buffer the two kernels write)"""
     buf, off, sess = session_sets.packed_shapes(first)
     label = f"gpu shapes first {first} max_headers {maxh} impl{impl} layout {layout}"
-    got = rhp.fixup_gpu(buf, off, sess, maxh, impl, layout)
+    got = rhp.fixup_gpu(buf, off, sess, maxh, impl, layout, guard=guard)
     check(*got, buf, off, sess, label, max_headers=maxh, want=shapes_oracle(maxh, first))
     twin = rhp.fixup_cpu(buf, off, sess, maxh, impl == rhp.IMPL_DFA, layout, prefix=True)
     assert_same_fixup(got, twin, sess, int(off[-1]), label + " vs host twin", every_row=False)
