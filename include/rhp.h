@@ -396,7 +396,7 @@ int rhp_write_responses(const rhp_resp_batch_t *batch, void *stream);
  * as the aligned dwords that hold them.
  * RHP_BATCH_SPECULATIVE batches are refused (-EINVAL): after
  * rhp_fixup_sessions a slot's offsets are relative to req_start, not to
- * offsets[i]; classifying those slots is a follow-up.  Also -EINVAL: an empty
+ * offsets[i]; rhp_classify_sessions (below) classifies those slots.  Also -EINVAL: an empty
  * name or one longer than RHP_CLASSIFY_NAME_MAX, a count above its limit,
  * route text above RHP_CLASSIFY_TEXT_MAX, n_names == 0 && n_routes == 0, a
  * missing table or output.  n == 0 succeeds and launches nothing.
@@ -428,6 +428,44 @@ typedef struct rhp_classify {
 } rhp_classify_t;
 
 int rhp_classify_batch(const rhp_batch_t *batch, const rhp_classify_t *c, void *stream);
+
+/*
+ * The same lookup and route match over pipelined input: `batch` is a
+ * RHP_BATCH_SPECULATIVE http batch exactly as rhp_parse_batch and
+ * rhp_fixup_sessions left it on `stream`; sessions, results (as
+ * rhp_fixup_sessions wrote them) and req_start (u64 [n], the same) are the
+ * fix-up's arguments, device memory.  Outputs as rhp_classify_batch, indexed by
+ * record slot: fields[j * n + i] and route[i] for every i < batch->n.
+ *   Slot i is in use when some session s has
+ *   piece_lo(s) <= i < piece_lo(s) + results[s].n_slots.  An in-use slot whose
+ *   http[i].result == 1 and reqs[i].ret > 0 is ready and is classified as
+ *   rhp_classify_batch documents, with one difference: the request's first
+ *   byte is req_start[i], not offsets[i] (the value spans are offsets from
+ *   there).  A ready request lies inside its session's input,
+ *   offsets[piece_lo] <= req_start[i] and req_start[i] + ret <=
+ *   offsets[piece_hi]; a slot whose records say otherwise is absent.
+ *   Every other slot -- one that is not in use, a session's last slot that
+ *   stopped on 0 / -1 / RHP_RET_TOOLONG, every slot when n_sessions == 0 --
+ *   gets {RHP_NAME_NULL, 0} for every name and RHP_ROUTE_NONE.  Of a slot that
+ *   is not in use neither the records nor req_start[i] are read: they hold
+ *   stale speculative records or nothing at all, and nobody has to zero them.
+ * The bytes are read through bytes_rw when it is set (the fix-up de-frames
+ * chunked bodies in place; a header section does not move).
+ * Contract: `sessions` is in ascending piece_lo order with disjoint
+ * [piece_lo, piece_hi) ranges (one session's pieces follow the previous
+ * one's).  When the order is violated a slot may be reported absent; nothing
+ * outside the batch's buffers is read.
+ * -EINVAL: a batch that is not RHP_MODE_HTTP or whose flags are not exactly
+ * RHP_BATCH_SPECULATIVE; anything rhp_parse_batch refuses for such a batch
+ * (which leaves RHP_LAYOUT_REQUEST_MAJOR and RHP_LAYOUT_HEADER_MAJOR);
+ * n_sessions > 0 with a NULL sessions, results or req_start; every table and
+ * output rule of rhp_classify_batch.  n == 0 succeeds and launches nothing;
+ * bytes_rw may be NULL.  Launch contract as rhp_classify_batch: one launch,
+ * no copy, no allocation, no synchronisation.
+ */
+int rhp_classify_sessions(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
+                          const rhp_session_result_t *results, const uint64_t *req_start,
+                          const rhp_classify_t *c, void *stream);
 
 
 #ifdef __cplusplus

@@ -21,6 +21,8 @@
  *                         RHP_LAYOUT_DENSE) as rhp_http_t
  *   rhp_cpu_classify_batch  rhp_classify_batch (rhp.h) over a parsed batch in
  *                         host memory, written over the three rhp_expand_*
+ *   rhp_cpu_classify_sessions  rhp_classify_sessions (rhp.h) over the slots a
+ *                         host fix-up left in a speculative batch
  *
  *   rhp_phr_parse_request the same exact parser with phr_parse_request's own
  *                         signature and outputs (pointers into buf, no length
@@ -62,6 +64,15 @@ int rhp_cpu_pack_dense(const rhp_batch_t *batch, rhp_req_dense_t *dreq, rhp_http
  * pointers, and c->fields and c->route, are host memory.  The same results
  * and the same -22 for refused arguments (the GPU tests compare the two). */
 int rhp_cpu_classify_batch(const rhp_batch_t *batch, const rhp_classify_t *c);
+/* rhp_classify_sessions (rhp.h) on the host: `batch` is the speculative batch a
+ * host parse and rhp_cpu_fixup_sessions / rhp_emu_fixup_sessions left, and
+ * every pointer is host memory.  The same results and the same -22.  The
+ * slots in use are found by a walk over the sessions, one after the other (the
+ * kernel searches sessions[].piece_lo): the two share the argument check and
+ * nothing else, and this one gives the right answers for sessions in any order. */
+int rhp_cpu_classify_sessions(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
+                              const rhp_session_result_t *results, const uint64_t *req_start,
+                              const rhp_classify_t *c);
 
 /* A parsed batch's header records as rhp_hdr_t, out[i * max_headers + k]
  * (request-major), from host copies of its reqs and hdrs in the batch's

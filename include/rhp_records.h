@@ -9,8 +9,9 @@
  * rhp_classify_args.h), rhp_pack_dense_kernel, the host library (rhp_host.cpp),
  * the emulator (rhp_emu.cpp) and the reactor (reactor/batch.c).  Two decodes are
  * deliberately their own: rhp_dfa_kernel's stores (a shared helper moves its
- * register allocation) and rhp_classify_kernel's word-level decode (the host
- * classify, written over this header, is what its tests compare it with).
+ * register allocation) and the word-level decode of rhp_classify_kernel and
+ * rhp_classify_sessions_kernel (the host classify, written over this header,
+ * is what their tests compare them with).
  */
 #ifndef RHP_RECORDS_H
 #define RHP_RECORDS_H

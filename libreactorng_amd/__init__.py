@@ -65,12 +65,12 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 
 # exported C-ABI symbols of librhp.so, as declared in include/rhp.h
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
-               "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch")
+               "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
                 "rhp_cpu_classify_batch", "rhp_emu_fixup_sessions", "rhp_test_fixup_whole", "rhp_test_chunk_window",
-                "rhp_test_chunk_exact")
+                "rhp_test_chunk_exact", "rhp_cpu_classify_sessions")
 
 _rhp = None
 _host = None
@@ -166,6 +166,9 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_pack_dense.restype = ctypes.c_int
         _rhp.rhp_classify_batch.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Classify), vp]
         _rhp.rhp_classify_batch.restype = ctypes.c_int
+        _rhp.rhp_classify_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp,
+                                               ctypes.POINTER(Classify), vp]
+        _rhp.rhp_classify_sessions.restype = ctypes.c_int
     return _rhp
 
 
@@ -210,6 +213,9 @@ def host() -> ctypes.CDLL:
         _host.rhp_expand_http.restype = ctypes.c_int
         _host.rhp_cpu_classify_batch.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Classify)]
         _host.rhp_cpu_classify_batch.restype = ctypes.c_int
+        _host.rhp_cpu_classify_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp,
+                                                    ctypes.POINTER(Classify)]
+        _host.rhp_cpu_classify_sessions.restype = ctypes.c_int
     return _host
 
 
@@ -875,6 +881,74 @@ def fixup_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_DFA, l
             gst.check()
         out = res, dres.cpu().numpy().view(SESSION_RESULT_DTYPE), dst.cpu().numpy().view(np.uint64)
         return out + (db,) if with_batch else out
+    finally:
+        lib().rhp_set_impl(IMPL_DFA)
+
+
+def classify_sessions_cpu(b_or_res, sessions, results, starts, names, routes=()):
+    """rhp_cpu_classify_sessions (include/rhp_host.h) over a speculative batch in
+    host memory after a fix-up: the Batch of speculative_cpu, or a Result that
+    describes its batch (fixup_cpu's, fixup_gpu's), with the fix-up's session
+    results and req_start.  Returns (fields FIELDREF_DTYPE [n_names, n], route
+    u16 [n]) by record slot."""
+    b = b_or_res.batch if isinstance(b_or_res, Result) else b_or_res
+    if b is None:
+        raise ValueError("this Result does not describe its batch")
+    text, nm, rt = classify_tables(names, routes)
+    n = b.n
+    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
+    results = np.ascontiguousarray(results, dtype=SESSION_RESULT_DTYPE)
+    starts = np.ascontiguousarray(starts, dtype=np.uint64)
+    fields = np.zeros((len(nm), n), dtype=FIELDREF_DTYPE)
+    route = np.zeros(n, dtype=np.uint16)
+    c = Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm), len(rt),
+                 _ptr(fields) if len(nm) else None, _ptr(route) if len(rt) else None)
+    rc = host().rhp_cpu_classify_sessions(ctypes.byref(b), _ptr(sessions), len(sessions), _ptr(results), _ptr(starts),
+                                          ctypes.byref(c))
+    if rc != 0:
+        raise RuntimeError(f"rhp_cpu_classify_sessions failed: {rc}")
+    if not len(rt):
+        route[:] = ROUTE_NONE
+    return fields, route
+
+
+def classify_sessions_gpu(buf, off, sessions, names, routes=(), max_headers: int = 16, impl: int = IMPL_DFA,
+                          layout: int = LAYOUT_REQUEST_MAJOR, fill: int | None = None):
+    """Speculative http batch on the GPU + rhp_fixup_sessions +
+    rhp_classify_sessions, three launches on one stream.  Returns (fields, route)
+    as classify_sessions_cpu, then what fixup_gpu returns: (Result, session
+    results, req_start).  fill (a byte, tests): the record buffers, req_start and
+    the session results hold it before the first launch, so that a slot the
+    fix-up never wrote reads back as that byte."""
+    import torch
+    lib().rhp_set_impl(impl)
+    try:
+        db = DeviceBatch(buf, off, max_headers, MODE_HTTP, layout=layout, flags=BATCH_SPECULATIVE, fill=fill)
+        ds = torch.from_numpy(np.ascontiguousarray(sessions).view(np.uint8).copy()).to("cuda")
+        dres = Guarded("results", len(sessions) * SESSION_RESULT_DTYPE.itemsize, fill=fill).view
+        dst = Guarded("req_start", max(db.n, 1) * 8, fill=fill).view
+        text, nm, rt = classify_tables(names, routes)
+        # (the outputs hold 0xA5 first: the kernel writes every slot)
+        fields = torch.full((max(len(nm) * db.n, 1) * FIELDREF_DTYPE.itemsize,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
+        route = torch.full((max(db.n, 1) * 2,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
+        c = Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm), len(rt),
+                     fields.data_ptr() if len(nm) else None, route.data_ptr() if len(rt) else None)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        vp = ctypes.c_void_p
+        db.launch()
+        d = db.desc()
+        rc = lib().rhp_fixup_sessions(ctypes.byref(d), vp(ds.data_ptr()), len(sessions), vp(dres.data_ptr()),
+                                      vp(dst.data_ptr()), stream)
+        if rc != 0:
+            raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
+        rc = lib().rhp_classify_sessions(ctypes.byref(d), vp(ds.data_ptr()), len(sessions), vp(dres.data_ptr()),
+                                         vp(dst.data_ptr()), ctypes.byref(c), stream)
+        if rc != 0:
+            raise RuntimeError(f"rhp_classify_sessions failed: {rc}")
+        res = db.result()   # (synchronizes)
+        f = fields.cpu().numpy()[: len(nm) * db.n * 4].view(FIELDREF_DTYPE).reshape(len(nm), db.n)
+        r = (route.cpu().numpy().view(np.uint16)[: db.n] if len(rt) else np.full(db.n, ROUTE_NONE, dtype=np.uint16))
+        return f, r, res, dres.cpu().numpy().view(SESSION_RESULT_DTYPE), dst.cpu().numpy().view(np.uint64)
     finally:
         lib().rhp_set_impl(IMPL_DFA)
 

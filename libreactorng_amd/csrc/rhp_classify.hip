@@ -18,6 +18,11 @@
  *
  * Nothing of a request that is not ready, and no record k >= num_headers, is
  * used: those are unspecified (rhp.h) and may hold anything.
+ *
+ * rhp_classify_sessions (rhp.h) is a second kernel beside it, for the record
+ * slots rhp_fixup_sessions leaves in a speculative batch: one slot per lane,
+ * the slot's session by binary search over sessions[].piece_lo, the request's
+ * first byte from req_start[i]; the same tables, compare and outputs.
  */
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -251,6 +256,142 @@ __global__ __launch_bounds__(256) void rhp_classify_kernel(CParams p)
   }
 }
 
+/* rhp_classify_sessions: the same lookup over the record slots rhp_fixup_sessions
+ * left.  The kernel's own argument: the tables lead it as they lead CParams. */
+struct SParams {
+  CTables         t;
+  const uint8_t  *bytes;
+  const uint64_t *offsets;
+  const uint8_t  *reqs, *hdrs, *http;
+  uint32_t       *fields;
+  uint16_t       *route;
+  const rhp_session_t        *sessions;
+  const rhp_session_result_t *results;
+  const uint64_t *req_start;
+  uint32_t        n, m, layout, n_names, n_routes, n_sessions;
+};
+static_assert(offsetof(SParams, t) == 0, "the tables lead the argument");
+static_assert(sizeof(SParams) <= 4096, "a kernel argument holds 4 KiB");
+
+/* One record slot per lane.  The lane finds the last session whose piece_lo is
+ * at or below its slot (sessions ascend by piece_lo, rhp.h) and tests that the
+ * slot is one the fix-up filled for that session; only then are req_start[i]
+ * and the slot's records loaded -- a slot the walk did not use holds a stale
+ * speculative record or nothing.  Whatever the search returns, it is the test
+ * that lets a load through, so sessions in any order read nothing outside the
+ * batch's buffers (a slot may then be reported absent).  rhp_hdr_t records
+ * only, request-major or header-major: the layouts of a speculative batch. */
+__global__ __launch_bounds__(256) void rhp_classify_sessions_kernel(SParams p)
+{
+  __shared__ uint32_t tab[kTabDwords];
+  __shared__ uint16_t lenmask[RHP_CLASSIFY_NAME_MAX + 1u];
+  {
+#if defined(__HIP_DEVICE_COMPILE__)   /* (as rhp_classify_kernel) */
+    const ka32 *ka = (const ka32 *) __builtin_amdgcn_kernarg_segment_ptr();
+#else
+    const ka32 *ka = nullptr;
+#endif
+    for (uint32_t t = threadIdx.x; t < kTabDwords; t += blockDim.x) tab[t] = ka[t];
+    if (threadIdx.x <= RHP_CLASSIFY_NAME_MAX) {
+      const ka32 *nl = ka + offsetof(CTables, name_len) / 4u;
+      uint32_t mk = 0;
+      for (uint32_t j = 0; j < p.n_names; j++) mk |= (((nl[j >> 2] >> (8u * (j & 3u))) & 0xffu) == threadIdx.x ? 1u : 0u) << j;
+      lenmask[threadIdx.x] = (uint16_t) mk;
+    }
+  }
+  __syncthreads();
+  const uint32_t *names = tab + offsetof(CTables, name) / 4u, *text = tab + offsetof(CTables, text) / 4u;
+  const uint16_t *r_moff = reinterpret_cast<const uint16_t *>(tab + offsetof(CTables, r_moff) / 4u);
+  const uint16_t *r_mlen = reinterpret_cast<const uint16_t *>(tab + offsetof(CTables, r_mlen) / 4u);
+  const uint16_t *r_toff = reinterpret_cast<const uint16_t *>(tab + offsetof(CTables, r_toff) / 4u);
+  const uint16_t *r_tlen = reinterpret_cast<const uint16_t *>(tab + offsetof(CTables, r_tlen) / 4u);
+
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = p.n, m = p.m;
+  if (i >= n) return;
+
+  /* ---- the slot's session: the sessions before `above` have piece_lo <= i ---- */
+  uint32_t above = 0;
+  for (uint32_t hi = p.n_sessions; above < hi;) {
+    const uint32_t mid = above + ((hi - above) >> 1);
+    if (p.sessions[mid].piece_lo <= i) above = mid + 1u; else hi = mid;
+  }
+
+  /* ---- in use?  ready?  then the request record and the request's first byte ---- */
+  int32_t ret = 0;
+  uint32_t method_off = 0, method_len = 0, path_off = 0, path_len = 0, nh = 0;
+  uint64_t at0 = 0;
+  bool ready = false;
+  if (above) {
+    const uint2 se = reinterpret_cast<const uint2 *>(p.sessions)[above - 1u];   /* piece_lo, piece_hi */
+    const uint32_t n_slots = p.results[above - 1u].n_slots;
+    /* (se.y <= n: offsets[piece_hi] is an entry of offsets) */
+    if (se.x <= i && i - se.x < n_slots && se.x <= se.y && se.y <= n &&
+        *reinterpret_cast<const int32_t *>(p.http + (size_t) i * sizeof(rhp_http_t)) == 1) {
+      const uint4 q = reinterpret_cast<const uint4 *>(p.reqs)[i];
+      ret = (int32_t) q.x;
+      if (ret > 0) {   /* RHP_RET_TOOLONG is negative */
+        /* the request lies inside its session's input */
+        const uint64_t rs = p.req_start[i], b_lo = p.offsets[se.x], b_hi = p.offsets[se.y];
+        ready = rs >= b_lo && rs <= b_hi && (uint64_t) (uint32_t) ret <= b_hi - rs;
+        at0 = rs;
+      }
+      if (ready) {
+        method_len = q.y & 0xffffu;
+        path_off = q.y >> 16;
+        path_len = q.z & 0xffffu;
+        method_off = (q.z >> 16) & 0xffu;
+        nh = q.w & 0xffffu;
+      }
+    }
+  }
+  if (nh > m) nh = m;   /* never more records than the batch holds */
+
+  /* ---- header lookup (rhp_classify_kernel's, over rhp_hdr_t records) ---- */
+  const uint32_t all = (1u << p.n_names) - 1u;
+  uint32_t found = 0;
+  if (p.n_names) {
+    uint64_t s_req = m, s_hdr = 1;   /* record k of slot i: index i * s_req + k * s_hdr */
+    if (p.layout == RHP_LAYOUT_HEADER_MAJOR) {
+      s_req = 1;
+      s_hdr = n;
+    }
+    for (uint32_t k = 0; k < nh && found != all; k++) {
+      const uint2 h = reinterpret_cast<const uint2 *>(p.hdrs)[(uint64_t) i * s_req + (uint64_t) k * s_hdr];
+      const uint32_t noff = h.x & 0xffffu, nl = h.x >> 16, voff = h.y & 0xffffu, vl = h.y >> 16;
+      if (noff == RHP_NAME_NULL) continue;   /* name == NULL: an obs-fold line */
+      uint32_t cand = nl <= RHP_CLASSIFY_NAME_MAX ? (uint32_t) lenmask[nl] & ~found : 0u;
+      if (cand == 0) continue;
+      if (noff + nl > (uint32_t) ret) continue;   /* (a parsed name lies inside its header section) */
+      cand = same_text<true>(p.bytes + at0 + noff, nl, cand, names, [](uint32_t j) { return j * kNameDwords; });
+      for (uint32_t c = cand; c; c &= c - 1u) p.fields[(uint64_t) __builtin_ctz(c) * n + i] = voff | vl << 16;
+      found |= cand;
+    }
+    for (uint32_t c = all & ~found; c; c &= c - 1u) p.fields[(uint64_t) __builtin_ctz(c) * n + i] = RHP_NAME_NULL;
+  }
+
+  /* ---- route match ---- */
+  if (p.route) {
+    uint32_t rt = RHP_ROUTE_NONE;
+    if (ready && p.n_routes) {
+      uint32_t cand = 0, with_method = 0;
+      for (uint32_t r = 0; r < p.n_routes; r++) {
+        const uint32_t ml = r_mlen[r];
+        if (r_tlen[r] == path_len && (ml == 0 || ml == method_len)) cand |= 1u << r;
+        if (ml) with_method |= 1u << r;
+      }
+      if (path_off + path_len > (uint32_t) ret || method_off + method_len > (uint32_t) ret) cand = 0;   /* (as the names) */
+      if (cand) cand = same_text<false>(p.bytes + at0 + path_off, path_len, cand, text, [&](uint32_t r) { return (uint32_t) r_toff[r]; });
+      if (cand & with_method) {
+        const uint32_t ok = same_text<false>(p.bytes + at0 + method_off, method_len, cand & with_method, text,
+                                             [&](uint32_t r) { return (uint32_t) r_moff[r]; });
+        cand = (cand & ~with_method) | ok;
+      }
+      if (cand) rt = (uint32_t) __builtin_ctz(cand);
+    }
+    p.route[i] = (uint16_t) rt;
+  }
+}
+
 /* the caller's tables as the kernel's: names folded, route text packed */
 void pack_tables(const rhp_classify_t *c, CTables &t)
 {
@@ -300,5 +441,34 @@ extern "C" int rhp_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c,
   p.n_names = c->n_names;
   p.n_routes = c->n_routes;
   hipLaunchKernelGGL(rhp_classify_kernel, dim3((b->n + 255u) / 256u), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
+  return (int) hipGetLastError();
+}
+
+extern "C" int rhp_classify_sessions(const rhp_batch_t *b, const rhp_session_t *sessions, uint32_t n_sessions,
+                                     const rhp_session_result_t *results, const uint64_t *req_start,
+                                     const rhp_classify_t *c, void *stream)
+{
+  const int rc = rhp_classify_sessions_check(b, sessions, n_sessions, results, req_start, c);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  SParams p;
+  pack_tables(c, p.t);
+  p.bytes = b->bytes_rw ? b->bytes_rw : b->bytes;
+  p.offsets = b->offsets;
+  p.reqs = reinterpret_cast<const uint8_t *>(b->reqs);
+  p.hdrs = reinterpret_cast<const uint8_t *>(b->hdrs);
+  p.http = reinterpret_cast<const uint8_t *>(b->http);
+  p.fields = reinterpret_cast<uint32_t *>(c->fields);
+  p.route = c->route;
+  p.sessions = sessions;
+  p.results = results;
+  p.req_start = req_start;
+  p.n = b->n;
+  p.m = b->max_headers;
+  p.layout = b->layout;
+  p.n_names = c->n_names;
+  p.n_routes = c->n_routes;
+  p.n_sessions = n_sessions;
+  hipLaunchKernelGGL(rhp_classify_sessions_kernel, dim3((b->n + 255u) / 256u), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), p);
   return (int) hipGetLastError();
 }

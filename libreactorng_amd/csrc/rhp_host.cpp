@@ -202,6 +202,70 @@ extern "C" int rhp_cpu_classify_batch(const rhp_batch_t *b, const rhp_classify_t
   return 0;
 }
 
+/* rhp_classify_sessions (rhp.h) on the host, over the speculative batch
+ * rhp_cpu_parse_batch / rhp_emu_parse_batch and a host fix-up left in host
+ * memory.  Every slot is absent first; then the sessions are walked one after
+ * the other and the slots each one filled, piece_lo .. piece_lo + n_slots, are
+ * classified from req_start[slot] -- no search, so the walk takes the sessions
+ * in any order.  The same plain loops as rhp_cpu_classify_batch over the
+ * rhp_hdr_t records (a speculative batch has no other kind). */
+extern "C" int rhp_cpu_classify_sessions(const rhp_batch_t *b, const rhp_session_t *sessions, uint32_t n_sessions,
+                                         const rhp_session_result_t *results, const uint64_t *req_start,
+                                         const rhp_classify_t *c)
+{
+  const int rc = rhp_classify_sessions_check(b, sessions, n_sessions, results, req_start, c);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const uint32_t n = b->n, m = b->max_headers;
+  const uint8_t *bytes = b->bytes_rw ? b->bytes_rw : b->bytes;
+  for (uint32_t i = 0; i < n; i++) {
+    for (uint32_t j = 0; j < c->n_names; j++) c->fields[(size_t) j * n + i] = rhp_fieldref_t{RHP_NAME_NULL, 0};
+    if (c->route) c->route[i] = RHP_ROUTE_NONE;
+  }
+  const auto upper = [](uint8_t x) { return x >= 'a' && x <= 'z' ? (uint8_t) (x - ('a' - 'A')) : x; };   /* C-locale toupper */
+  const auto same = [&](const uint8_t *s, uint32_t len, rhp_span_t t) {
+    return len == t.len && (len == 0 || memcmp(s, c->text + t.off, len) == 0);
+  };
+  for (uint32_t s = 0; s < n_sessions; s++) {
+    const uint32_t lo = sessions[s].piece_lo, hi = sessions[s].piece_hi;
+    if (lo > hi || hi > n) continue;   /* not a session of this batch */
+    for (uint32_t q = 0; q < results[s].n_slots && q < n - lo; q++) {
+      const uint32_t i = lo + q;
+      const rhp_req_t &r = b->reqs[i];
+      if (b->http[i].result != 1 || r.ret <= 0) continue;
+      /* the request lies inside its session's input */
+      const uint64_t at = req_start[i], ret = (uint64_t) r.ret;
+      if (at < b->offsets[lo] || at > b->offsets[hi] || ret > b->offsets[hi] - at) continue;
+      const uint8_t *req = bytes + at;
+      const uint32_t nh = r.num_headers < m ? r.num_headers : m;
+      for (uint32_t j = 0; j < c->n_names; j++) {
+        const uint8_t *name = c->text + c->names[j].off;
+        const uint32_t len = c->names[j].len;
+        for (uint32_t k = 0; k < nh; k++) {
+          const rhp_hdr_t &h = RHP_HDR(b->hdrs, b->layout, n, m, i, k);
+          if (h.name_off == RHP_NAME_NULL || h.name_len != len) continue;
+          if ((uint64_t) h.name_off + len > ret) continue;   /* (a parsed name lies inside its header section) */
+          uint32_t x = 0;
+          while (x < len && upper(req[h.name_off + x]) == upper(name[x])) x++;
+          if (x == len) {
+            c->fields[(size_t) j * n + i] = rhp_fieldref_t{h.value_off, h.value_len};
+            break;
+          }
+        }
+      }
+      if (!c->route) continue;
+      if ((uint64_t) r.path_off + r.path_len > ret || (uint64_t) r.method_off + r.method_len > ret) continue;
+      for (uint32_t k = 0; k < c->n_routes; k++) {
+        const rhp_route_t &t = c->routes[k];
+        if (same(req + r.path_off, r.path_len, t.target) && (t.method.len == 0 || same(req + r.method_off, r.method_len, t.method))) {
+          c->route[i] = (uint16_t) k;
+          break;
+        }
+      }
+    }
+  }
+  return 0;
+}
+
 /* ---- the pointer-based host parser: phr_parse_request's own outputs ---- */
 
 namespace {

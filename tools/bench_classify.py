@@ -12,7 +12,15 @@ fraction of the HBM peak that is at the median time.
 
 Without --config every config runs in a child process of its own under a time
 limit, one after the other, and the first failure ends the run.
+
+--sessions times rhp_classify_sessions instead (rhp_classify.hip's second
+kernel): rounds of TFB GETs as sessions x pipelined requests (64 x 64, 256 x
+256, 4096 x 1, 65536 x 1), each parsed as a speculative batch; rhp_fixup_sessions
+and rhp_classify_sessions between HIP events, and for comparison
+rhp_classify_batch over the same requests parsed as a non-speculative
+request-major batch.  One JSON line per round, a child process each.
 usage: python tools/bench_classify.py [--config get256|zipf|post] [--n N] [--reps K] [--warmup W]
+       python tools/bench_classify.py --sessions [--round SESSIONS PER_SESSION] [--reps K] [--warmup W]
 """
 import argparse
 import json
@@ -147,13 +155,116 @@ def run(key, n, reps, warmup):
         "input_bytes": int(off[-1]), "librhp_sha256": rhp.library_sha256()}), flush=True)
 
 
+TFB = (b"GET /plaintext HTTP/1.1\r\nHost: tfb-server:8080\r\nAccept: text/plain\r\n"
+       b"Connection: keep-alive\r\nUser-Agent: wrk/4.2.0 (tfb-load)\r\n\r\n")
+SESSION_ROUTES = ((b"GET", b"/plaintext"), (None, b"/c"), (b"POST", b"/cl"), (b"GET", b"/inside-a-body"))
+SESSION_ROUNDS = ((64, 64), (256, 256), (4096, 1), (65536, 1))   # sessions x pipelined requests per session
+
+
+def run_sessions(n_sessions, per_session, reps, warmup):
+    """One round of TFB GETs as the reactor batches it: a speculative parse, then
+    rhp_fixup_sessions and rhp_classify_sessions, each between HIP events; next
+    to it rhp_classify_batch over the same requests parsed as a non-speculative
+    request-major batch (every piece of this round is one request, so the two
+    batches have the same offsets)."""
+    import ctypes
+    import torch
+    maxh = 16
+    one = TFB * per_session
+    buf, off, sess, _ = rhp.pack_sessions([one] * n_sessions,
+                                          split=lambda data: [len(TFB)] * per_session)   # (the server's split of it)
+    n = len(off) - 1
+    assert n == n_sessions * per_session
+    vp = ctypes.c_void_p
+    spec = rhp.DeviceBatch(buf, off, maxh, rhp.MODE_HTTP, layout=rhp.LAYOUT_REQUEST_MAJOR, flags=rhp.BATCH_SPECULATIVE)
+    plain = rhp.DeviceBatch(buf, off, maxh, rhp.MODE_HTTP, layout=rhp.LAYOUT_REQUEST_MAJOR)
+    ds = torch.from_numpy(sess.view(np.uint8).copy()).to("cuda")
+    dres = torch.zeros(n_sessions * rhp.SESSION_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    dst = torch.zeros(n * 8, dtype=torch.uint8, device="cuda")
+    text, nm, rt = rhp.classify_tables(NAMES, SESSION_ROUTES)
+    fields = torch.zeros(len(nm) * n * 4, dtype=torch.uint8, device="cuda")
+    route = torch.zeros(n, dtype=torch.int16, device="cuda")
+    c = rhp.Classify(text.ctypes.data, nm.ctypes.data, rt.ctypes.data, len(nm), len(rt), fields.data_ptr(), route.data_ptr())
+    d = spec.desc()
+    plain_launch, plain_fields, plain_route = plain.classifier(NAMES, SESSION_ROUTES)
+    s = torch.cuda.current_stream()
+    sp = vp(s.cuda_stream)
+    lib = rhp.lib()
+
+    def fixup():
+        rc = lib.rhp_fixup_sessions(ctypes.byref(d), vp(ds.data_ptr()), n_sessions, vp(dres.data_ptr()), vp(dst.data_ptr()), sp)
+        assert rc == 0, rc
+
+    def classify():
+        rc = lib.rhp_classify_sessions(ctypes.byref(d), vp(ds.data_ptr()), n_sessions, vp(dres.data_ptr()),
+                                       vp(dst.data_ptr()), ctypes.byref(c), sp)
+        assert rc == 0, rc
+
+    def once(ev=None):
+        mark = (lambda k: ev[k].record(s)) if ev else (lambda k: None)
+        spec.launch()
+        mark(0)
+        fixup()
+        mark(1)
+        classify()
+        mark(2)
+        plain.launch()
+        mark(3)
+        plain_launch()
+        mark(4)
+
+    for _ in range(warmup):
+        once()
+    torch.cuda.synchronize()
+    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(5)] for _ in range(reps)]
+    for ev in evs:
+        once(ev)
+    torch.cuda.synchronize()
+    us = lambda a, b: np.array([ev[a].elapsed_time(ev[b]) for ev in evs]) * 1e3
+    fix, cls, base = us(0, 1), us(1, 2), us(3, 4)
+    # the classification itself: the host twin over the records the GPU left, and the plain batch's kernel
+    f = fields.cpu().numpy().view(rhp.FIELDREF_DTYPE).reshape(len(nm), n)
+    r = route.cpu().numpy().view(np.uint16)
+    results = dres.cpu().numpy().view(rhp.SESSION_RESULT_DTYPE)
+    starts = dst.cpu().numpy().view(np.uint64)
+    cf, cr = rhp.classify_sessions_cpu(spec.result(), sess, results, starts, NAMES, SESSION_ROUTES)
+    assert np.array_equal(f, cf) and np.array_equal(r, cr), "the kernel and the host twin differ"
+    pf = plain_fields.cpu().numpy()[: len(nm) * n * 4].view(rhp.FIELDREF_DTYPE).reshape(len(nm), n)
+    assert np.array_equal(f, pf) and np.array_equal(r, plain_route.cpu().numpy().view(np.uint16)[:n]), \
+        "rhp_classify_sessions and rhp_classify_batch differ"
+    assert (r == 0).all() and (results["n_slots"] == per_session).all()
+    med = lambda a: round(float(np.median(a)), 2)
+    print(json.dumps({
+        "leg": "sessions", "sessions": n_sessions, "requests_per_session": per_session, "slots": n, "reps": reps,
+        "warmup": warmup, "fixup_us_median": med(fix), "fixup_us_min": round(float(fix.min()), 2),
+        "classify_sessions_us_median": med(cls), "classify_sessions_us_min": round(float(cls.min()), 2),
+        "classify_batch_us_median": med(base), "classify_batch_us_min": round(float(base.min()), 2),
+        "sessions_over_batch_median": round(float(np.median(cls)) / float(np.median(base)), 3),
+        "input_bytes": int(off[-1]), "librhp_sha256": rhp.library_sha256()}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sessions", action="store_true",
+                    help="the rhp_classify_sessions leg: SESSION_ROUNDS of TFB GETs (--round S K: one of them)")
+    ap.add_argument("--round", type=int, nargs=2, default=None, metavar=("SESSIONS", "PER_SESSION"))
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None)
     ap.add_argument("--n", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args()
+    if a.sessions and a.round:
+        run_sessions(a.round[0], a.round[1], a.reps, a.warmup)
+        return 0
+    if a.sessions:   # as the configs: a fresh process per round, under its own limit; stop at the first failure
+        for n_sessions, per_session in SESSION_ROUNDS:
+            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--sessions", "--round", str(n_sessions),
+                                 str(per_session), "--reps", str(a.reps), "--warmup", str(a.warmup)],
+                                timeout=CHILD_LIMIT_S).returncode
+            if rc != 0:
+                print(f"bench_classify: round {n_sessions} x {per_session} ended with status {rc}; stopping", file=sys.stderr)
+                return rc
+        return 0
     if a.config:
         run(a.config, a.n, a.reps, a.warmup)
         return 0
