@@ -646,15 +646,13 @@ class DeviceBatch:
         fields tensor u8 [n_names * n * 4], route tensor i16 [n] or None).  Each
         launch() is one asynchronous call on the stream (default: the current one)."""
         import torch
-        text, nm, rt = classify_tables(names, routes)
         dev = self.reqs.device
-        fields = torch.zeros(max(len(nm) * self.n, 1) * FIELDREF_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        route = torch.zeros(max(self.n, 1), dtype=torch.int16, device=dev) if len(rt) else None
-        c = Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm), len(rt),
-                     fields.data_ptr() if len(nm) else None, route.data_ptr() if route is not None else None)
+        fields = torch.zeros(max(len(names) * self.n, 1) * FIELDREF_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        route = torch.zeros(max(self.n, 1), dtype=torch.int16, device=dev) if len(routes) else None
+        *keep, c = _classify_desc(names, routes, fields.data_ptr(), route.data_ptr() if route is not None else None)
         d = self.desc()
 
-        def launch(stream=None, _keep=(text, nm, rt)):
+        def launch(stream=None, _keep=keep):
             s = stream if stream is not None else torch.cuda.current_stream()
             rc = lib().rhp_classify_batch(ctypes.byref(d), ctypes.byref(c), ctypes.c_void_p(s.cuda_stream))
             if rc != 0:
@@ -668,11 +666,7 @@ class DeviceBatch:
         launch, fields, route = self.classifier(names, routes)
         launch(stream)
         torch.cuda.synchronize()
-        n_names = len(names)
-        f = fields.cpu().numpy()[: n_names * self.n * 4].view(FIELDREF_DTYPE).reshape(n_names, self.n)
-        r = (route.cpu().numpy().view(np.uint16)[: self.n] if route is not None
-             else np.full(self.n, ROUTE_NONE, dtype=np.uint16))
-        return f, r
+        return _classify_out(fields, route, len(names), self.n)
 
 
 def parse_batch(buf: np.ndarray, off: np.ndarray, max_headers: int = 16, mode: int = MODE_PHR,
@@ -708,6 +702,26 @@ def classify_tables(names, routes=()):
     return text, nm, rt
 
 
+def _classify_desc(names, routes, fields_ptr, route_ptr):
+    """(text, names, routes, Classify): rhp_classify_t over classify_tables(names,
+    routes) and the two output buffers; a table or an output that nothing uses
+    is NULL.  The Classify points into the three arrays: keep them alive."""
+    text, nm, rt = classify_tables(names, routes)
+    return text, nm, rt, Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm),
+                                  len(rt), fields_ptr if len(nm) else None, route_ptr if len(rt) else None)
+
+
+def _classify_out(fields, route, n_names, n):
+    """The output buffers of a classify call, device tensors or numpy arrays, as
+    (fields FIELDREF_DTYPE [n_names, n], route u16 [n]); route None (no routes):
+    RHP_ROUTE_NONE everywhere."""
+    def u8(a):
+        return (a if isinstance(a, np.ndarray) else a.cpu().numpy()).reshape(-1).view(np.uint8)
+    f = u8(fields)[: n_names * n * FIELDREF_DTYPE.itemsize].view(FIELDREF_DTYPE).reshape(n_names, n)
+    r = u8(route)[: n * 2].view(np.uint16) if route is not None else np.full(n, ROUTE_NONE, dtype=np.uint16)
+    return f, r
+
+
 def classify_cpu(res_or_batch, names, routes=()):
     """rhp_cpu_classify_batch (include/rhp_host.h) over a parsed batch in host
     memory: a Result of emulate / parse_cpu_exact / parse_batch / DeviceBatch.result
@@ -716,16 +730,13 @@ def classify_cpu(res_or_batch, names, routes=()):
     b = res_or_batch.batch if isinstance(res_or_batch, Result) else res_or_batch
     if b is None:
         raise ValueError("this Result does not describe its batch")
-    text, nm, rt = classify_tables(names, routes)
-    n = b.n
-    fields = np.zeros((len(nm), n), dtype=FIELDREF_DTYPE)
-    route = np.full(n, ROUTE_NONE, dtype=np.uint16)
-    c = Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm), len(rt),
-                 _ptr(fields) if len(nm) else None, _ptr(route) if len(rt) else None)
+    fields = np.zeros((len(names), b.n), dtype=FIELDREF_DTYPE)
+    route = np.zeros(b.n, dtype=np.uint16)
+    *_keep, c = _classify_desc(names, routes, _ptr(fields), _ptr(route))
     rc = host().rhp_cpu_classify_batch(ctypes.byref(b), ctypes.byref(c))
     if rc != 0:
         raise RuntimeError(f"rhp_cpu_classify_batch failed: {rc}")
-    return fields, route
+    return _classify_out(fields, route if len(routes) else None, len(names), b.n)
 
 
 def classify_batch(buf: np.ndarray, off: np.ndarray, names, routes=(), max_headers: int = 16, mode: int = MODE_PHR,
@@ -894,22 +905,17 @@ def classify_sessions_cpu(b_or_res, sessions, results, starts, names, routes=())
     b = b_or_res.batch if isinstance(b_or_res, Result) else b_or_res
     if b is None:
         raise ValueError("this Result does not describe its batch")
-    text, nm, rt = classify_tables(names, routes)
-    n = b.n
     sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
     results = np.ascontiguousarray(results, dtype=SESSION_RESULT_DTYPE)
     starts = np.ascontiguousarray(starts, dtype=np.uint64)
-    fields = np.zeros((len(nm), n), dtype=FIELDREF_DTYPE)
-    route = np.zeros(n, dtype=np.uint16)
-    c = Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm), len(rt),
-                 _ptr(fields) if len(nm) else None, _ptr(route) if len(rt) else None)
+    fields = np.zeros((len(names), b.n), dtype=FIELDREF_DTYPE)
+    route = np.zeros(b.n, dtype=np.uint16)
+    *_keep, c = _classify_desc(names, routes, _ptr(fields), _ptr(route))
     rc = host().rhp_cpu_classify_sessions(ctypes.byref(b), _ptr(sessions), len(sessions), _ptr(results), _ptr(starts),
                                           ctypes.byref(c))
     if rc != 0:
         raise RuntimeError(f"rhp_cpu_classify_sessions failed: {rc}")
-    if not len(rt):
-        route[:] = ROUTE_NONE
-    return fields, route
+    return _classify_out(fields, route if len(routes) else None, len(names), b.n)
 
 
 def classify_sessions_gpu(buf, off, sessions, names, routes=(), max_headers: int = 16, impl: int = IMPL_DFA,
@@ -927,12 +933,10 @@ def classify_sessions_gpu(buf, off, sessions, names, routes=(), max_headers: int
         ds = torch.from_numpy(np.ascontiguousarray(sessions).view(np.uint8).copy()).to("cuda")
         dres = Guarded("results", len(sessions) * SESSION_RESULT_DTYPE.itemsize, fill=fill).view
         dst = Guarded("req_start", max(db.n, 1) * 8, fill=fill).view
-        text, nm, rt = classify_tables(names, routes)
         # (the outputs hold 0xA5 first: the kernel writes every slot)
-        fields = torch.full((max(len(nm) * db.n, 1) * FIELDREF_DTYPE.itemsize,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
+        fields = torch.full((max(len(names) * db.n, 1) * FIELDREF_DTYPE.itemsize,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
         route = torch.full((max(db.n, 1) * 2,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
-        c = Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm), len(rt),
-                     fields.data_ptr() if len(nm) else None, route.data_ptr() if len(rt) else None)
+        *_keep, c = _classify_desc(names, routes, fields.data_ptr(), route.data_ptr())
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         vp = ctypes.c_void_p
         db.launch()
@@ -946,9 +950,8 @@ def classify_sessions_gpu(buf, off, sessions, names, routes=(), max_headers: int
         if rc != 0:
             raise RuntimeError(f"rhp_classify_sessions failed: {rc}")
         res = db.result()   # (synchronizes)
-        f = fields.cpu().numpy()[: len(nm) * db.n * 4].view(FIELDREF_DTYPE).reshape(len(nm), db.n)
-        r = (route.cpu().numpy().view(np.uint16)[: db.n] if len(rt) else np.full(db.n, ROUTE_NONE, dtype=np.uint16))
-        return f, r, res, dres.cpu().numpy().view(SESSION_RESULT_DTYPE), dst.cpu().numpy().view(np.uint64)
+        out = _classify_out(fields, route if len(routes) else None, len(names), db.n)
+        return out + (res, dres.cpu().numpy().view(SESSION_RESULT_DTYPE), dst.cpu().numpy().view(np.uint64))
     finally:
         lib().rhp_set_impl(IMPL_DFA)
 

@@ -19,10 +19,12 @@
  * Nothing of a request that is not ready, and no record k >= num_headers, is
  * used: those are unspecified (rhp.h) and may hold anything.
  *
- * rhp_classify_sessions (rhp.h) is a second kernel beside it, for the record
- * slots rhp_fixup_sessions leaves in a speculative batch: one slot per lane,
- * the slot's session by binary search over sessions[].piece_lo, the request's
- * first byte from req_start[i]; the same tables, compare and outputs.
+ * rhp_classify_sessions (rhp.h) is the same lookup over the record slots
+ * rhp_fixup_sessions leaves in a speculative batch: one slot per lane, the
+ * slot's session by binary search over sessions[].piece_lo, the request's
+ * first byte from req_start[i].  Its kernel restates the first one's table load,
+ * compare, absent fill and route match; stating them once is deferred (DESIGN
+ * 3.5).  The launchers share fill_params.
  */
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -49,7 +51,7 @@ constexpr uint32_t kTabDwords = sizeof(CTables) / 4u;
 static_assert(sizeof(CTables) % 4u == 0 && offsetof(CTables, name_len) % 4u == 0, "copied to LDS as dwords");
 
 struct CParams {
-  CTables         t;          /* first: the kernel reads it from the start of its argument segment */
+  CTables         t;          /* first: the kernels read it from the start of their argument segment */
   const uint8_t  *bytes;
   const uint64_t *offsets;
   const uint8_t  *reqs, *hdrs, *http;
@@ -256,8 +258,8 @@ __global__ __launch_bounds__(256) void rhp_classify_kernel(CParams p)
   }
 }
 
-/* rhp_classify_sessions: the same lookup over the record slots rhp_fixup_sessions
- * left.  The kernel's own argument: the tables lead it as they lead CParams. */
+/* rhp_classify_sessions_kernel's argument: CParams' members under their names
+ * (fill_params fills either), with what the session search needs among them */
 struct SParams {
   CTables         t;
   const uint8_t  *bytes;
@@ -346,7 +348,7 @@ __global__ __launch_bounds__(256) void rhp_classify_sessions_kernel(SParams p)
   }
   if (nh > m) nh = m;   /* never more records than the batch holds */
 
-  /* ---- header lookup (rhp_classify_kernel's, over rhp_hdr_t records) ---- */
+  /* ---- header lookup over rhp_hdr_t records ---- */
   const uint32_t all = (1u << p.n_names) - 1u;
   uint32_t found = 0;
   if (p.n_names) {
@@ -369,7 +371,7 @@ __global__ __launch_bounds__(256) void rhp_classify_sessions_kernel(SParams p)
     for (uint32_t c = all & ~found; c; c &= c - 1u) p.fields[(uint64_t) __builtin_ctz(c) * n + i] = RHP_NAME_NULL;
   }
 
-  /* ---- route match ---- */
+  /* ---- route match: lengths first, then the path's and the method's bytes ---- */
   if (p.route) {
     uint32_t rt = RHP_ROUTE_NONE;
     if (ready && p.n_routes) {
@@ -420,19 +422,16 @@ void pack_tables(const rhp_classify_t *c, CTables &t)
   }
 }
 
-}  // namespace
-
-extern "C" int rhp_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c, void *stream)
+/* what CParams and SParams share; which bytes and whether http is the caller's */
+template <class P>
+void fill_params(P &p, const rhp_batch_t *b, const rhp_classify_t *c, const uint8_t *bytes, const rhp_http_t *http)
 {
-  const int rc = rhp_classify_check(b, c);
-  if (rc != 0) return rc < 0 ? rc : 0;
-  CParams p;
   pack_tables(c, p.t);
-  p.bytes = b->mode == RHP_MODE_HTTP && b->bytes_rw ? b->bytes_rw : b->bytes;
+  p.bytes = bytes;
   p.offsets = b->offsets;
   p.reqs = reinterpret_cast<const uint8_t *>(b->reqs);
   p.hdrs = reinterpret_cast<const uint8_t *>(b->hdrs);
-  p.http = b->mode == RHP_MODE_HTTP ? reinterpret_cast<const uint8_t *>(b->http) : nullptr;
+  p.http = reinterpret_cast<const uint8_t *>(http);
   p.fields = reinterpret_cast<uint32_t *>(c->fields);
   p.route = c->route;
   p.n = b->n;
@@ -440,6 +439,17 @@ extern "C" int rhp_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c,
   p.layout = b->layout;
   p.n_names = c->n_names;
   p.n_routes = c->n_routes;
+}
+
+}  // namespace
+
+extern "C" int rhp_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c, void *stream)
+{
+  const int rc = rhp_classify_check(b, c);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const bool http_mode = b->mode == RHP_MODE_HTTP;
+  CParams p;
+  fill_params(p, b, c, http_mode && b->bytes_rw ? b->bytes_rw : b->bytes, http_mode ? b->http : nullptr);
   hipLaunchKernelGGL(rhp_classify_kernel, dim3((b->n + 255u) / 256u), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
   return (int) hipGetLastError();
 }
@@ -451,22 +461,10 @@ extern "C" int rhp_classify_sessions(const rhp_batch_t *b, const rhp_session_t *
   const int rc = rhp_classify_sessions_check(b, sessions, n_sessions, results, req_start, c);
   if (rc != 0) return rc < 0 ? rc : 0;
   SParams p;
-  pack_tables(c, p.t);
-  p.bytes = b->bytes_rw ? b->bytes_rw : b->bytes;
-  p.offsets = b->offsets;
-  p.reqs = reinterpret_cast<const uint8_t *>(b->reqs);
-  p.hdrs = reinterpret_cast<const uint8_t *>(b->hdrs);
-  p.http = reinterpret_cast<const uint8_t *>(b->http);
-  p.fields = reinterpret_cast<uint32_t *>(c->fields);
-  p.route = c->route;
+  fill_params(p, b, c, b->bytes_rw ? b->bytes_rw : b->bytes, b->http);   /* (a speculative batch is an http one) */
   p.sessions = sessions;
   p.results = results;
   p.req_start = req_start;
-  p.n = b->n;
-  p.m = b->max_headers;
-  p.layout = b->layout;
-  p.n_names = c->n_names;
-  p.n_routes = c->n_routes;
   p.n_sessions = n_sessions;
   hipLaunchKernelGGL(rhp_classify_sessions_kernel, dim3((b->n + 255u) / 256u), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), p);

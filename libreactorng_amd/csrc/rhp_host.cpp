@@ -143,13 +143,67 @@ extern "C" int rhp_cpu_pack_dense(const rhp_batch_t *b, rhp_req_dense_t *dreq, r
   return 0;
 }
 
-/* rhp_classify_batch (rhp.h) on the host, over a parsed batch in host memory:
+namespace {
+
+/* slot i of the classification as an absent request has it */
+void classify_absent(const rhp_classify_t *c, uint32_t n, uint32_t i)
+{
+  for (uint32_t j = 0; j < c->n_names; j++) c->fields[(size_t) j * n + i] = rhp_fieldref_t{RHP_NAME_NULL, 0};
+  if (c->route) c->route[i] = RHP_ROUTE_NONE;
+}
+
+/* Slot i of the classification, absent on entry (classify_absent), for one
+ * ready request (r.ret > 0) whose first byte is req[0] and whose header record
+ * k < min(r.num_headers, m) is hdr(k):
  * http_field_lookup (src/reactor/http.c:167-175: the first field whose name is
  * string_equal_case, src/reactor/data.c:11-28) per name and the first route
- * whose target and method are string_equal, one request and one byte at a
- * time over the records as rhp_expand_reqs / rhp_expand_records /
- * rhp_expand_http give them -- a decode of the layouts that shares nothing
- * with the kernel's (rhp_classify.hip). */
+ * whose target and method are string_equal, one byte at a time.  Both host
+ * twins classify here.  As in the kernels (rhp_classify.hip),
+ * no byte outside [req, req + ret) is read: a name that ends
+ * past ret matches nothing, and a path or method that does takes no route.
+ * No parsed record is like that; rhp_cpu_classify_batch used to read such
+ * offsets as they stood, where its kernel did not. */
+template <class Hdr>
+void classify_one(const rhp_classify_t *c, uint32_t n, uint32_t m, uint32_t i, const uint8_t *req, const rhp_req_t &r, Hdr hdr)
+{
+  const uint64_t ret = (uint64_t) r.ret;
+  const uint32_t nh = r.num_headers < m ? r.num_headers : m;
+  const auto upper = [](uint8_t x) { return x >= 'a' && x <= 'z' ? (uint8_t) (x - ('a' - 'A')) : x; };   /* C-locale toupper */
+  const auto same = [&](const uint8_t *s, uint32_t len, rhp_span_t t) {
+    return len == t.len && (len == 0 || memcmp(s, c->text + t.off, len) == 0);
+  };
+  for (uint32_t j = 0; j < c->n_names; j++) {
+    const uint8_t *name = c->text + c->names[j].off;
+    const uint32_t len = c->names[j].len;
+    for (uint32_t k = 0; k < nh; k++) {
+      const rhp_hdr_t &h = hdr(k);
+      if (h.name_off == RHP_NAME_NULL || h.name_len != len) continue;
+      if ((uint64_t) h.name_off + len > ret) continue;   /* (a parsed name lies inside its header section) */
+      uint32_t q = 0;
+      while (q < len && upper(req[h.name_off + q]) == upper(name[q])) q++;
+      if (q == len) {
+        c->fields[(size_t) j * n + i] = rhp_fieldref_t{h.value_off, h.value_len};
+        break;
+      }
+    }
+  }
+  if (!c->route) return;
+  if ((uint64_t) r.path_off + r.path_len > ret || (uint64_t) r.method_off + r.method_len > ret) return;
+  for (uint32_t k = 0; k < c->n_routes; k++) {
+    const rhp_route_t &t = c->routes[k];
+    if (same(req + r.path_off, r.path_len, t.target) && (t.method.len == 0 || same(req + r.method_off, r.method_len, t.method))) {
+      c->route[i] = (uint16_t) k;
+      break;
+    }
+  }
+}
+
+}  // namespace
+
+/* rhp_classify_batch (rhp.h) on the host, over a parsed batch in host memory:
+ * classify_one per ready request, over the records as rhp_expand_reqs /
+ * rhp_expand_records / rhp_expand_http give them -- a decode of the layouts
+ * that shares nothing with the kernel's (rhp_classify.hip). */
 extern "C" int rhp_cpu_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c)
 {
   const int rc = rhp_classify_check(b, c);
@@ -163,41 +217,10 @@ extern "C" int rhp_cpu_classify_batch(const rhp_batch_t *b, const rhp_classify_t
   if (m && rhp_expand_records(b, reqs.data(), b->hdrs, hdrs.data()) != 0) return -22;
   if (http_mode && rhp_expand_http(b, reqs.data(), b->http, http.data()) != 0) return -22;
   const uint8_t *bytes = http_mode && b->bytes_rw ? b->bytes_rw : b->bytes;
-  const auto upper = [](uint8_t x) { return x >= 'a' && x <= 'z' ? (uint8_t) (x - ('a' - 'A')) : x; };   /* C-locale toupper */
-  const auto same = [&](const uint8_t *s, uint32_t len, rhp_span_t t) {
-    return len == t.len && (len == 0 || memcmp(s, c->text + t.off, len) == 0);
-  };
   for (uint32_t i = 0; i < n; i++) {
-    const rhp_req_t &r = reqs[i];
-    const bool ready = r.ret > 0 && (!http_mode || http[i].result == 1);
-    const uint8_t *req = bytes + b->offsets[i];
-    const uint32_t nh = !ready ? 0u : r.num_headers < m ? r.num_headers : m;
-    for (uint32_t j = 0; j < c->n_names; j++) {
-      const uint8_t *name = c->text + c->names[j].off;
-      const uint32_t len = c->names[j].len;
-      rhp_fieldref_t f = {RHP_NAME_NULL, 0};
-      for (uint32_t k = 0; k < nh; k++) {
-        const rhp_hdr_t &h = hdrs[(size_t) i * m + k];
-        if (h.name_off == RHP_NAME_NULL || h.name_len != len) continue;
-        uint32_t q = 0;
-        while (q < len && upper(req[h.name_off + q]) == upper(name[q])) q++;
-        if (q == len) {
-          f = rhp_fieldref_t{h.value_off, h.value_len};
-          break;
-        }
-      }
-      c->fields[(size_t) j * n + i] = f;
-    }
-    if (!c->route) continue;
-    uint16_t rt = RHP_ROUTE_NONE;
-    for (uint32_t k = 0; ready && k < c->n_routes; k++) {
-      const rhp_route_t &t = c->routes[k];
-      if (same(req + r.path_off, r.path_len, t.target) && (t.method.len == 0 || same(req + r.method_off, r.method_len, t.method))) {
-        rt = (uint16_t) k;
-        break;
-      }
-    }
-    c->route[i] = rt;
+    classify_absent(c, n, i);
+    if (reqs[i].ret > 0 && (!http_mode || http[i].result == 1))
+      classify_one(c, n, m, i, bytes + b->offsets[i], reqs[i], [&](uint32_t k) -> const rhp_hdr_t & { return hdrs[(size_t) i * m + k]; });
   }
   return 0;
 }
@@ -206,9 +229,10 @@ extern "C" int rhp_cpu_classify_batch(const rhp_batch_t *b, const rhp_classify_t
  * rhp_cpu_parse_batch / rhp_emu_parse_batch and a host fix-up left in host
  * memory.  Every slot is absent first; then the sessions are walked one after
  * the other and the slots each one filled, piece_lo .. piece_lo + n_slots, are
- * classified from req_start[slot] -- no search, so the walk takes the sessions
- * in any order.  The same plain loops as rhp_cpu_classify_batch over the
- * rhp_hdr_t records (a speculative batch has no other kind). */
+ * classified (classify_one) from req_start[slot] -- no search, so the walk
+ * takes the sessions in any order.  That a request lies inside its session's
+ * input is tested here, before classify_one reads a byte of it.  rhp_hdr_t
+ * records only (a speculative batch has no other kind). */
 extern "C" int rhp_cpu_classify_sessions(const rhp_batch_t *b, const rhp_session_t *sessions, uint32_t n_sessions,
                                          const rhp_session_result_t *results, const uint64_t *req_start,
                                          const rhp_classify_t *c)
@@ -217,14 +241,7 @@ extern "C" int rhp_cpu_classify_sessions(const rhp_batch_t *b, const rhp_session
   if (rc != 0) return rc < 0 ? rc : 0;
   const uint32_t n = b->n, m = b->max_headers;
   const uint8_t *bytes = b->bytes_rw ? b->bytes_rw : b->bytes;
-  for (uint32_t i = 0; i < n; i++) {
-    for (uint32_t j = 0; j < c->n_names; j++) c->fields[(size_t) j * n + i] = rhp_fieldref_t{RHP_NAME_NULL, 0};
-    if (c->route) c->route[i] = RHP_ROUTE_NONE;
-  }
-  const auto upper = [](uint8_t x) { return x >= 'a' && x <= 'z' ? (uint8_t) (x - ('a' - 'A')) : x; };   /* C-locale toupper */
-  const auto same = [&](const uint8_t *s, uint32_t len, rhp_span_t t) {
-    return len == t.len && (len == 0 || memcmp(s, c->text + t.off, len) == 0);
-  };
+  for (uint32_t i = 0; i < n; i++) classify_absent(c, n, i);
   for (uint32_t s = 0; s < n_sessions; s++) {
     const uint32_t lo = sessions[s].piece_lo, hi = sessions[s].piece_hi;
     if (lo > hi || hi > n) continue;   /* not a session of this batch */
@@ -233,34 +250,9 @@ extern "C" int rhp_cpu_classify_sessions(const rhp_batch_t *b, const rhp_session
       const rhp_req_t &r = b->reqs[i];
       if (b->http[i].result != 1 || r.ret <= 0) continue;
       /* the request lies inside its session's input */
-      const uint64_t at = req_start[i], ret = (uint64_t) r.ret;
-      if (at < b->offsets[lo] || at > b->offsets[hi] || ret > b->offsets[hi] - at) continue;
-      const uint8_t *req = bytes + at;
-      const uint32_t nh = r.num_headers < m ? r.num_headers : m;
-      for (uint32_t j = 0; j < c->n_names; j++) {
-        const uint8_t *name = c->text + c->names[j].off;
-        const uint32_t len = c->names[j].len;
-        for (uint32_t k = 0; k < nh; k++) {
-          const rhp_hdr_t &h = RHP_HDR(b->hdrs, b->layout, n, m, i, k);
-          if (h.name_off == RHP_NAME_NULL || h.name_len != len) continue;
-          if ((uint64_t) h.name_off + len > ret) continue;   /* (a parsed name lies inside its header section) */
-          uint32_t x = 0;
-          while (x < len && upper(req[h.name_off + x]) == upper(name[x])) x++;
-          if (x == len) {
-            c->fields[(size_t) j * n + i] = rhp_fieldref_t{h.value_off, h.value_len};
-            break;
-          }
-        }
-      }
-      if (!c->route) continue;
-      if ((uint64_t) r.path_off + r.path_len > ret || (uint64_t) r.method_off + r.method_len > ret) continue;
-      for (uint32_t k = 0; k < c->n_routes; k++) {
-        const rhp_route_t &t = c->routes[k];
-        if (same(req + r.path_off, r.path_len, t.target) && (t.method.len == 0 || same(req + r.method_off, r.method_len, t.method))) {
-          c->route[i] = (uint16_t) k;
-          break;
-        }
-      }
+      const uint64_t at = req_start[i];
+      if (at < b->offsets[lo] || at > b->offsets[hi] || (uint64_t) r.ret > b->offsets[hi] - at) continue;
+      classify_one(c, n, m, i, bytes + at, r, [&](uint32_t k) -> const rhp_hdr_t & { return RHP_HDR(b->hdrs, b->layout, n, m, i, k); });
     }
   }
   return 0;
