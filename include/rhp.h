@@ -467,6 +467,89 @@ int rhp_classify_sessions(const rhp_batch_t *batch, const rhp_session_t *session
                           const rhp_session_result_t *results, const uint64_t *req_start,
                           const rhp_classify_t *c, void *stream);
 
+/*
+ * Static routes answered on the device: from route[] (rhp_classify_sessions'
+ * output) and the fix-up's results straight to each session's reply bytes,
+ * ready for one D2H copy and one write() per session.  A static route's reply
+ * is one byte string per round (the date is one per batch), so the caller
+ * serializes one response per route with rhp_write_responses whenever the date
+ * changes; that call's `out` and `out_off` are the reply images here.  The
+ * replies of a session lie back to back in request order, as the reference
+ * appends them to the stream (src/reactor/server.c:174, http.c:248, 276).
+ *   batch, sessions, n_sessions, results: rhp_classify_sessions' arguments;
+ *   route: its output, device u16 [n].
+ *   Slot i is static when route[i] < table->n_routes and bit route[i] of
+ *   static_mask is set (rhp_classify_sessions writes RHP_ROUTE_NONE to every
+ *   slot that is not an in-use, ready request; a value >= n_routes is not
+ *   static and never indexes image_off).
+ *   count(s) is the length of the leading run of static slots in
+ *   [piece_lo, piece_lo + results[s].n_slots): the run stops at the first
+ *   request the host must answer, since a later reply cannot be sent ahead of
+ *   it.  count(s) is 0 when the session's walk stopped on -1 (n_slots >= 1 and
+ *   http[piece_lo + n_slots - 1].result == -1: the reference closes such a
+ *   session without flushing what it wrote, server.c:47-51, 64; this is the
+ *   only record of the batch that is read), and for a session whose fields do
+ *   not satisfy piece_lo <= piece_lo + n_slots <= piece_hi <= n.
+ *   out holds the sessions' replies in ascending session index, each
+ *   session's in request order: out_off(s) is the sum of the earlier sessions'
+ *   out_len, out_len(s) the sum of its answered slots' image lengths (an empty
+ *   image is an answered request).  replies[s] for every s < n_sessions and
+ *   *total are always written.
+ * Contract: `sessions` ascends by piece_lo with disjoint ranges, as for
+ * rhp_classify_sessions.  With that order violated the answers are unspecified;
+ * still nothing is read outside the arguments' buffers and nothing is written
+ * outside replies[0, n_sessions), total, work and out[0, out_size).
+ * The images are read as the aligned dwords that hold them: no byte outside
+ * images[image_off[0], image_off[n_routes]) rounded out to 4-byte boundaries
+ * (the `out` of rhp_write_responses inside an allocation whose start and size
+ * are multiples of 4 is readable so), and none of an image whose route is not
+ * in static_mask or is not answered.
+ * -EINVAL: whatever rhp_classify_sessions refuses about the batch, sessions and
+ * results; a NULL route, table, o, image_off, replies, total or work; n_routes
+ * 0 or above RHP_CLASSIFY_MAX_ROUTES; a NULL out with out_size > 0; a NULL
+ * images unless every image is empty (the host twin, rhp_host.h, checks the
+ * lengths; the device entry cannot read image_off and with a NULL images copies
+ * no image byte at all).  n_sessions == 0 writes *total = 0 and nothing else;
+ * n == 0 with sessions gives every session count 0.
+ * Launch contract as rhp_classify_sessions: asynchronous on `stream`, no
+ * allocation, no host synchronisation, no copy; thread-safe.  Four launches
+ * (tile sums, one workgroup's scan of them, the tiles' scan, copy with the
+ * per-session records), as rhp_write_responses; two when n == 0, one when
+ * n_sessions == 0.
+ */
+typedef struct rhp_reply_table {
+  const uint8_t  *images;      /* device: serialized replies back to back, any alignment
+                                  (rhp_write_responses' `out` for n_routes responses) */
+  const uint64_t *image_off;   /* device [n_routes + 1], non-decreasing (its `out_off`):
+                                  route r's reply is images[image_off[r], image_off[r+1]) */
+  uint32_t        n_routes;    /* 1..RHP_CLASSIFY_MAX_ROUTES: the classify call's n_routes */
+  uint32_t        static_mask; /* bit r set: route r is answered here; clear: the host answers it */
+} rhp_reply_table_t;
+
+typedef struct rhp_session_reply {     /* 24 B */
+  uint32_t count;     /* the session's first `count` requests (slots piece_lo .. piece_lo+count-1) are answered */
+  uint32_t reserved;  /* written 0 */
+  uint64_t out_off;   /* their replies, in request order: out[out_off, out_off + out_len) */
+  uint64_t out_len;
+} rhp_session_reply_t;
+
+typedef struct rhp_reply_out {
+  rhp_session_reply_t *replies;  /* device [n_sessions] */
+  uint64_t            *total;    /* device [1]: sum of every out_len */
+  uint8_t             *out;      /* device, out_size bytes, any alignment */
+  uint64_t             out_size; /* when *total > out_size nothing is written to `out`; replies and total are still
+                                    complete (grow and call again), as rhp_write_responses */
+  uint64_t            *work;     /* device scratch, >= RHP_REPLY_WORK_WORDS(n, n_sessions) u64 */
+} rhp_reply_out_t;
+
+/* per slot an offset (and one more), per 64 slots a mask, per 256 slots three words of its tile's sum */
+#define RHP_REPLY_WORK_WORDS(n, n_sessions) \
+  ((uint64_t) (n) + 1u + ((uint64_t) (n) + 63u) / 64u + 3u * (((uint64_t) (n) + 255u) / 256u) + 0u * (uint64_t) (n_sessions))
+
+int rhp_reply_sessions(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
+                       const rhp_session_result_t *results, const uint16_t *route,
+                       const rhp_reply_table_t *table, const rhp_reply_out_t *o, void *stream);
+
 
 #ifdef __cplusplus
 }

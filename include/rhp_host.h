@@ -94,6 +94,16 @@ int rhp_expand_reqs(const rhp_batch_t *batch, const void *reqs, rhp_req_t *out);
  * rhp_http_compact_t; consumed from reqs[i].ret).  0, or -22. */
 int rhp_expand_http(const rhp_batch_t *batch, const rhp_req_t *reqs, const void *http, rhp_http_t *out);
 
+/* rhp_reply_sessions (rhp.h) over a speculative batch in host memory after a
+ * host fix-up and classify: every pointer of the arguments is host memory, there
+ * is no stream, `work` is not used (it must still be there, as for the device
+ * call).  A sequential walk over the sessions; it shares only the argument check
+ * with the kernels.  A NULL `images` is refused unless every image is empty.
+ * 0, or -22. */
+int rhp_cpu_reply_sessions(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
+                           const rhp_session_result_t *results, const uint16_t *route,
+                           const rhp_reply_table_t *table, const rhp_reply_out_t *o);
+
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */
 typedef struct rhp_phr_header {
   const char *name;

@@ -65,12 +65,12 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 
 # exported C-ABI symbols of librhp.so, as declared in include/rhp.h
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
-               "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions")
+               "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
                 "rhp_cpu_classify_batch", "rhp_emu_fixup_sessions", "rhp_test_fixup_whole", "rhp_test_chunk_window",
-                "rhp_test_chunk_exact", "rhp_cpu_classify_sessions")
+                "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions")
 
 _rhp = None
 _host = None
@@ -97,6 +97,27 @@ class Classify(ctypes.Structure):
 CLASSIFY_MAX_NAMES, CLASSIFY_NAME_MAX, CLASSIFY_MAX_ROUTES, CLASSIFY_TEXT_MAX = 16, 64, 32, 2048
 ROUTE_NONE = 0xFFFF
 FIELDREF_DTYPE = np.dtype([("value_off", "<u2"), ("value_len", "<u2")])   # absent: (RHP_NAME_NULL, 0)
+
+
+class ReplyTable(ctypes.Structure):
+    """rhp_reply_table_t (include/rhp.h): the reply images of the static routes"""
+    _fields_ = [("images", ctypes.c_void_p), ("image_off", ctypes.c_void_p), ("n_routes", ctypes.c_uint32),
+                ("static_mask", ctypes.c_uint32)]
+
+
+class ReplyOut(ctypes.Structure):
+    """rhp_reply_out_t (include/rhp.h): the outputs of rhp_reply_sessions"""
+    _fields_ = [("replies", ctypes.c_void_p), ("total", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("out_size", ctypes.c_uint64), ("work", ctypes.c_void_p)]
+
+
+SESSION_REPLY_DTYPE = np.dtype([("count", "<u4"), ("reserved", "<u4"), ("out_off", "<u8"), ("out_len", "<u8")])
+assert SESSION_REPLY_DTYPE.itemsize == 24 and ctypes.sizeof(ReplyTable) == 24 and ctypes.sizeof(ReplyOut) == 40
+
+
+def reply_work_words(n: int, n_sessions: int = 0) -> int:
+    """RHP_REPLY_WORK_WORDS (include/rhp.h)"""
+    return n + 1 + (n + 63) // 64 + 3 * ((n + 255) // 256)
 
 
 def _torch_hip_runtime() -> str | None:
@@ -169,6 +190,9 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_classify_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp,
                                                ctypes.POINTER(Classify), vp]
         _rhp.rhp_classify_sessions.restype = ctypes.c_int
+        _rhp.rhp_reply_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp,
+                                            ctypes.POINTER(ReplyTable), ctypes.POINTER(ReplyOut), vp]
+        _rhp.rhp_reply_sessions.restype = ctypes.c_int
     return _rhp
 
 
@@ -216,6 +240,9 @@ def host() -> ctypes.CDLL:
         _host.rhp_cpu_classify_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp,
                                                     ctypes.POINTER(Classify)]
         _host.rhp_cpu_classify_sessions.restype = ctypes.c_int
+        _host.rhp_cpu_reply_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp,
+                                                 ctypes.POINTER(ReplyTable), ctypes.POINTER(ReplyOut)]
+        _host.rhp_cpu_reply_sessions.restype = ctypes.c_int
     return _host
 
 
@@ -1144,3 +1171,155 @@ def write_responses(arena: np.ndarray, resps: np.ndarray, fields: np.ndarray, da
     d = DeviceResponses(arena, resps, fields, date)
     d.launch()
     return d.result()
+
+
+# ---------------------------------------------------------------------------
+# Static routes answered on the device (rhp.h rhp_reply_sessions): route[] and the
+# fix-up's results -> every session's reply bytes, copied from one serialized
+# reply per route (the `out` / `out_off` of a write_responses call).
+
+REPLY_POISON = 0xFF   # what replies, total, out and work hold before a call (tests)
+
+
+def _addr(a) -> int | None:
+    """the address of a numpy array's or a torch tensor's first element"""
+    if a is None:
+        return None
+    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+
+
+def reply_table(images, image_off, static_mask: int) -> ReplyTable:
+    """rhp_reply_table_t over `images` (u8) and `image_off` (u64 / i64 [n_routes + 1]): both numpy arrays (the
+    host twin) or both torch device tensors; slices are taken at their first element.  Keep them alive."""
+    return ReplyTable(_addr(images), _addr(image_off), len(image_off) - 1, static_mask)
+
+
+def response_sizes(resps, fields) -> np.ndarray:
+    """bytes of every serialized response of a make_responses-style batch (http.c:244-246, 270-272), on the host"""
+    r = np.asarray(resps, dtype=np.uint64).reshape(-1, 8)
+    fl = np.asarray(fields, dtype=np.uint64).reshape(-1, 4)
+    per = fl[:, 1] + fl[:, 3] + 4 if len(fl) else np.zeros(0, dtype=np.uint64)
+    extra = np.array([int(per[int(a): int(a) + int(c)].sum()) for a, c in zip(r[:, 6], r[:, 7])], dtype=np.uint64)
+    digits = np.array([len(str(int(v))) for v in r[:, 5]], dtype=np.uint64)
+    return 95 + r[:, 1] + r[:, 3] + r[:, 5] + digits + extra
+
+
+def reply_sessions_cpu(b_or_res, sessions, results, route, images, image_off, static_mask: int,
+                       out_size: int | None = None, out_shift: int = 0):
+    """rhp_cpu_reply_sessions (include/rhp_host.h) over a speculative batch in host memory after a fix-up and a
+    classify (the Batch of speculative_cpu or a Result that describes its batch; route u16 [n] by record slot).
+    Returns (replies SESSION_REPLY_DTYPE [n_sessions], total, out u8 [out_size]): every output held REPLY_POISON
+    before the call.  out_size None: the exact size, from a sizes-only call first.  out_shift: `out` starts that
+    many bytes after a 16-byte boundary."""
+    b = b_or_res.batch if isinstance(b_or_res, Result) else b_or_res
+    if b is None:
+        raise ValueError("this Result does not describe its batch")
+    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
+    results = np.ascontiguousarray(results, dtype=SESSION_RESULT_DTYPE)
+    route = np.ascontiguousarray(route, dtype=np.uint16)
+    image_off = np.ascontiguousarray(image_off, dtype=np.uint64)
+    t = reply_table(images, image_off, static_mask)
+    ns = len(sessions)
+    work = np.full(reply_work_words(b.n, ns), REPLY_POISON, dtype=np.uint8).repeat(8)
+
+    def call(size, shift):
+        replies = np.full(max(ns, 1) * SESSION_REPLY_DTYPE.itemsize, REPLY_POISON, dtype=np.uint8)
+        total = np.full(8, REPLY_POISON, dtype=np.uint8)
+        raw = np.full(size + shift + 16, REPLY_POISON, dtype=np.uint8)
+        at = (-raw.ctypes.data) % 16 + shift
+        out = raw[at: at + size]
+        o = ReplyOut(_ptr(replies), _ptr(total), _ptr(out) if size else None, size, _ptr(work))
+        rc = host().rhp_cpu_reply_sessions(ctypes.byref(b), _ptr(sessions), ns, _ptr(results), _ptr(route),
+                                           ctypes.byref(t), ctypes.byref(o))
+        if rc != 0:
+            raise RuntimeError(f"rhp_cpu_reply_sessions failed: {rc}")
+        return replies.view(SESSION_REPLY_DTYPE)[:ns], int(total.view(np.uint64)[0]), out
+
+    if out_size is None:
+        out_size = call(0, 0)[1]
+    return call(out_size, out_shift)
+
+
+def reply_sessions_device(d: Batch, sessions_t, n_sessions: int, results_t, route_t, images_t, image_off_t,
+                          static_mask: int, out_size: int, guard: int = 0, out_shift: int = 0, stream=None):
+    """One rhp_reply_sessions call over device buffers (torch tensors; `d` the parsed, fixed-up batch's descriptor)
+    on the stream (default: the current one).  replies, total, out and work are Guarded (guard bytes on both
+    sides, `out` out_shift bytes into its allocation) and hold REPLY_POISON first.  Returns finish(): synchronize,
+    check the guards, (replies SESSION_REPLY_DTYPE [n_sessions], total, out u8 [out_size])."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    g = {"replies": Guarded("replies", max(n_sessions, 1) * SESSION_REPLY_DTYPE.itemsize, guard, fill=REPLY_POISON),
+         "total": Guarded("total", 8, guard, fill=REPLY_POISON),
+         "out": Guarded("out", max(out_size, 1), guard, fill=REPLY_POISON, shift=out_shift),
+         "work": Guarded("work", reply_work_words(d.n, n_sessions) * 8, guard, fill=REPLY_POISON)}
+    t = reply_table(images_t, image_off_t, static_mask)
+    o = ReplyOut(g["replies"].view.data_ptr(), g["total"].view.data_ptr(), g["out"].view.data_ptr() if out_size else None,
+                 out_size, g["work"].view.data_ptr())
+    vp = ctypes.c_void_p
+    rc = lib().rhp_reply_sessions(ctypes.byref(d), vp(_addr(sessions_t)), n_sessions, vp(_addr(results_t)),
+                                  vp(_addr(route_t)), ctypes.byref(t), ctypes.byref(o), vp(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_reply_sessions failed: {rc}")
+
+    def finish(_keep=(sessions_t, results_t, route_t, images_t, image_off_t)):
+        torch.cuda.synchronize()
+        if guard:
+            for x in g.values():
+                x.check()
+        replies = g["replies"].view.cpu().numpy().view(SESSION_REPLY_DTYPE)[:n_sessions]
+        total = int(g["total"].view.cpu().numpy().view(np.uint64)[0])
+        return replies, total, g["out"].view.cpu().numpy()[:out_size]
+    return finish
+
+
+def reply_sessions_gpu(buf, off, sessions, names, routes, resps_for_routes, static_mask: int, max_headers: int = 16,
+                       impl: int = IMPL_DFA, layout: int = LAYOUT_REQUEST_MAJOR, guard: int = 0,
+                       out_size: int | None = None, out_shift: int = 0, date: bytes = DEFAULT_DATE, details: bool = False):
+    """A round of pipelined input answered on the GPU: speculative parse -> rhp_fixup_sessions ->
+    rhp_classify_sessions -> rhp_write_responses over resps_for_routes (arena, resps, fields: one response per
+    route, the reply images) -> rhp_reply_sessions, on one stream with no synchronisation in between.  out_size
+    None: every slot's worth of the largest image.  Returns (replies, total, out bytes) as reply_sessions_device;
+    details: also (Result, session results, route u16 [n]) as the GPU left them."""
+    import torch
+    arena, resps, fields = resps_for_routes
+    if len(resps) != len(routes):
+        raise ValueError("one response per route")
+    lib().rhp_set_impl(impl)
+    try:
+        db = DeviceBatch(buf, off, max_headers, MODE_HTTP, layout=layout, flags=BATCH_SPECULATIVE, guard=guard)
+        ns = len(sessions)
+        ds = torch.from_numpy(np.ascontiguousarray(sessions).view(np.uint8).copy()).to("cuda")
+        dres = Guarded("results", max(ns, 1) * SESSION_RESULT_DTYPE.itemsize, guard, fill=REPLY_POISON)
+        dst = Guarded("req_start", max(db.n, 1) * 8, guard, fill=REPLY_POISON)
+        droute = Guarded("route", max(db.n, 1) * 2, guard, fill=GUARD_BYTE)
+        *_keep, c = _classify_desc((), routes, None, droute.view.data_ptr())
+        images = DeviceResponses(arena, resps, fields, date)
+        if out_size is None:
+            out_size = db.n * int(response_sizes(resps, fields).max())
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        vp = ctypes.c_void_p
+        db.launch()
+        d = db.desc()
+        rc = lib().rhp_fixup_sessions(ctypes.byref(d), vp(ds.data_ptr()), ns, vp(dres.view.data_ptr()),
+                                      vp(dst.view.data_ptr()), stream)
+        if rc != 0:
+            raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
+        rc = lib().rhp_classify_sessions(ctypes.byref(d), vp(ds.data_ptr()), ns, vp(dres.view.data_ptr()),
+                                         vp(dst.view.data_ptr()), ctypes.byref(c), stream)
+        if rc != 0:
+            raise RuntimeError(f"rhp_classify_sessions failed: {rc}")
+        images.launch()
+        finish = reply_sessions_device(d, ds, ns, dres.view, droute.view, images.out, images.out_off, static_mask,
+                                       out_size, guard, out_shift)
+        out = finish()
+        if guard:
+            db.check_guards()
+            for x in (dres, dst, droute):
+                x.check()
+        if not details:
+            return out
+        res = db.result()
+        return out + (res, dres.view.cpu().numpy().view(SESSION_RESULT_DTYPE)[:ns],
+                      droute.view.cpu().numpy().view(np.uint16)[: db.n])
+    finally:
+        lib().rhp_set_impl(IMPL_DFA)

@@ -1,7 +1,7 @@
 /*
  * rhp_host.cpp -- the product's host entry points (rhp_host.h): the exact
  * scalar parser over a batch in host memory, the session fix-up, the dense
- * pack and the three expansions, the host classify, and the pointer-based
+ * pack and the three expansions, the host classify and reply, and the pointer-based
  * rhp_phr_parse_request / rhp_http_read_cpu.  libreactor.so links them.  The
  * parser is rhp_scalar.h's (the code the kernel's rare paths run); where the
  * records sit and how they are encoded is rhp_records.h's.
@@ -15,6 +15,7 @@
 #include "rhp_records.h"
 #include "rhp_scalar.h"
 #include "rhp_classify_args.h"
+#include "rhp_reply_args.h"
 #include "rhp_host_exact.h"
 
 using namespace rhp;
@@ -253,6 +254,47 @@ extern "C" int rhp_cpu_classify_sessions(const rhp_batch_t *b, const rhp_session
       const uint64_t at = req_start[i];
       if (at < b->offsets[lo] || at > b->offsets[hi] || (uint64_t) r.ret > b->offsets[hi] - at) continue;
       classify_one(c, n, m, i, bytes + at, r, [&](uint32_t k) -> const rhp_hdr_t & { return RHP_HDR(b->hdrs, b->layout, n, m, i, k); });
+    }
+  }
+  return 0;
+}
+
+/* rhp_reply_sessions (rhp.h) on the host, every pointer in host memory: a plain
+ * walk, session by session and slot by slot -- the leading run of static slots
+ * of a session whose fields hold and whose walk did not stop on -1, its sizes
+ * summed on the way; then, when the total fits, the images copied in the same
+ * order.  It shares the argument check with the kernels' launcher
+ * (rhp_reply_args.h) and nothing else. */
+extern "C" int rhp_cpu_reply_sessions(const rhp_batch_t *b, const rhp_session_t *sessions, uint32_t n_sessions,
+                                      const rhp_session_result_t *results, const uint16_t *route,
+                                      const rhp_reply_table_t *t, const rhp_reply_out_t *o)
+{
+  const int rc = rhp_reply_sessions_check(b, sessions, n_sessions, results, route, t, o, 1);
+  if (rc < 0) return rc;
+  const uint32_t n = rc == 1 ? 0 : b->n;
+  const auto is_static = [&](uint32_t r) { return r < t->n_routes && ((t->static_mask >> r) & 1u); };
+  uint64_t total = 0;
+  for (uint32_t s = 0; s < n_sessions; s++) {
+    const uint32_t lo = sessions[s].piece_lo, hi = sessions[s].piece_hi, ns = results[s].n_slots;
+    uint32_t count = 0;
+    uint64_t len = 0;
+    if ((uint64_t) lo + ns <= hi && hi <= n && ns >= 1 && b->http[lo + ns - 1u].result != -1)
+      for (; count < ns && is_static(route[lo + count]); count++) {
+        const uint32_t r = route[lo + count];
+        len += t->image_off[r + 1u] - t->image_off[r];
+      }
+    o->replies[s] = rhp_session_reply_t{count, 0, total, len};
+    total += len;
+  }
+  *o->total = total;
+  if (total > o->out_size) return 0;   /* sizes only */
+  for (uint32_t s = 0; s < n_sessions; s++) {
+    uint64_t at = o->replies[s].out_off;
+    for (uint32_t q = 0; q < o->replies[s].count; q++) {
+      const uint32_t r = route[sessions[s].piece_lo + q];
+      const uint64_t len = t->image_off[r + 1u] - t->image_off[r];
+      if (len) memcpy(o->out + at, t->images + t->image_off[r], len);
+      at += len;
     }
   }
   return 0;
