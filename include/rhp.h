@@ -550,6 +550,93 @@ int rhp_reply_sessions(const rhp_batch_t *batch, const rhp_session_t *sessions, 
                        const rhp_session_result_t *results, const uint16_t *route,
                        const rhp_reply_table_t *table, const rhp_reply_out_t *o, void *stream);
 
+/*
+ * The wide slots of a round in one contiguous area: after rhp_parse_batch,
+ * rhp_fixup_sessions and rhp_pack_dense, everything the host still needs about
+ * the slots the dense copies (dreq, hc, lens16) cannot hold -- their
+ * request-major records and the chunked bodies the fix-up de-framed -- is left
+ * in three small areas, so that one D2H copy of their used parts (with the
+ * dense copies) carries the whole round and nothing is fetched afterwards.
+ *   batch: the RHP_MODE_HTTP, RHP_LAYOUT_REQUEST_MAJOR, RHP_BATCH_SPECULATIVE
+ *   batch as the parse, the fix-up and rhp_pack_dense left it on `stream`;
+ *   sessions, results, req_start: the fix-up's arguments; dreq, hc: the pack's
+ *   outputs.  All device memory.
+ *   In use.  Slot i is in use exactly as rhp_classify_sessions defines it: some
+ *   session has piece_lo <= i < piece_lo + n_slots; a session whose fields do
+ *   not satisfy piece_lo <= piece_lo + n_slots <= piece_hi <= n owns nothing.
+ *   Wide.  An in-use slot is wide when hc[i].flags & RHP_HTTP_WIDE, or
+ *   hc[i].result == 1 && (dreq[i].flags & RHP_DENSE_WIDE).  A slot that is not
+ *   in use often carries a wide mark from a stale speculative record: it is
+ *   never gathered, and nothing of it but hc[i] and dreq[i] is read.
+ *   A wide slot's record (rhp_wide_slot_t, 64 B) holds reqs[i], http[i] and
+ *   req_start[i] as the batch holds them.
+ *   Headers.  n_hdrs(i) is req.num_headers when http.result == 1 && req.ret > 0
+ *   && req.num_headers <= max_headers, else 0; the slot's header records
+ *   batch->hdrs[i * max_headers + k], k < n_hdrs(i), are hdrs[hdr_first + k].
+ *   Body.  A wide slot has a body to gather when http.result == 1, body_kind ==
+ *   1, consumed != ret + body_len (mod 2^64, ret sign-extended: a chunked body
+ *   was de-framed in place) and, with a = req_start + ret (mod 2^64), the range
+ *   [a, a + body_len) lies inside its session's input:
+ *   offsets[piece_lo] <= a <= offsets[piece_hi] and body_len <=
+ *   offsets[piece_hi] - a.  Its bytes (read through bytes_rw when it is set) are
+ *   body[body_off, body_off + http.body_len).  Any other wide slot has body_off
+ *   == RHP_WIDE_NO_BODY and adds nothing to body_bytes.
+ *   Order.  Wide slots appear in ascending slot index; hdr_first and body_off
+ *   are the exclusive prefix sums of n_hdrs and of the gathered body lengths in
+ *   that order.
+ *   Totals.  *totals is always written and exact.  When n_wide > cap_slots,
+ *   n_hdrs > cap_hdrs or body_bytes > cap_body nothing is written to any of the
+ *   three areas (grow and call again, as rhp_write_responses and
+ *   rhp_reply_sessions).  n_sessions == 0 or n == 0: zero totals, nothing else.
+ * Contract: `sessions` ascends by piece_lo with disjoint ranges, as for
+ * rhp_classify_sessions.  With that order violated the answers are unspecified;
+ * still nothing is read outside the arguments' buffers and nothing is written
+ * outside totals, work, slots[0, cap_slots), hdrs[0, cap_hdrs) and
+ * body[0, cap_body).
+ * -EINVAL: whatever rhp_pack_dense or rhp_classify_sessions refuses about the
+ * batch, sessions and results (so any layout but RHP_LAYOUT_REQUEST_MAJOR; a
+ * NULL req_start with sessions); a NULL dreq, hc, o, totals or work; a NULL
+ * area with a non-zero cap; slots not 16-byte or hdrs not 8-byte aligned (the
+ * records leave as whole 16- and 8-byte stores; body: any alignment).
+ * Launch contract as rhp_reply_sessions: asynchronous on `stream`, no
+ * allocation, no host synchronisation, no copy; thread-safe.  Three launches
+ * (a wave's sums per 64 slots, one workgroup's scan of them with *totals, the
+ * offsets and the copy); one when n == 0 or n_sessions == 0.
+ */
+typedef struct rhp_wide_slot {   /* 64 B, no padding: one sector per wide slot */
+  uint32_t   slot;               /* record slot index i */
+  uint32_t   hdr_first;          /* its header records: hdrs[hdr_first .. + n_hdrs(i)) */
+  rhp_req_t  req;                /* reqs[i] */
+  rhp_http_t http;               /* http[i] */
+  uint64_t   req_start;          /* req_start[i] */
+  uint64_t   body_off;           /* body[body_off .. + http.body_len), or RHP_WIDE_NO_BODY */
+} rhp_wide_slot_t;
+#define RHP_WIDE_NO_BODY (~(uint64_t) 0)
+
+typedef struct rhp_wide_totals {   /* 16 B */
+  uint32_t n_wide, n_hdrs;
+  uint64_t body_bytes;
+} rhp_wide_totals_t;
+
+typedef struct rhp_wide_out {
+  rhp_wide_totals_t *totals;     /* device [1] */
+  rhp_wide_slot_t   *slots;      /* device [cap_slots], 16-byte aligned */
+  uint32_t           cap_slots;
+  rhp_hdr_t         *hdrs;       /* device [cap_hdrs], 8-byte aligned */
+  uint32_t           cap_hdrs;
+  uint8_t           *body;       /* device, cap_body bytes, any alignment */
+  uint64_t           cap_body;
+  uint64_t          *work;       /* device scratch, >= RHP_WIDE_WORK_WORDS(n) u64 */
+} rhp_wide_out_t;
+
+/* per 64 slots: three sums and two masks (wide, with a body) */
+#define RHP_WIDE_WORK_WORDS(n) (5u * (((uint64_t) (n) + 63u) / 64u) + 1u)
+
+int rhp_gather_wide(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
+                    const rhp_session_result_t *results, const uint64_t *req_start,
+                    const rhp_req_dense_t *dreq, const rhp_http_compact_t *hc,
+                    const rhp_wide_out_t *o, void *stream);
+
 
 #ifdef __cplusplus
 }

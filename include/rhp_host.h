@@ -23,6 +23,8 @@
  *                         host memory, written over the three rhp_expand_*
  *   rhp_cpu_classify_sessions  rhp_classify_sessions (rhp.h) over the slots a
  *                         host fix-up left in a speculative batch
+ *   rhp_cpu_reply_sessions, rhp_cpu_gather_wide  rhp_reply_sessions and
+ *                         rhp_gather_wide (rhp.h) as sequential walks
  *
  *   rhp_phr_parse_request the same exact parser with phr_parse_request's own
  *                         signature and outputs (pointers into buf, no length
@@ -103,6 +105,16 @@ int rhp_expand_http(const rhp_batch_t *batch, const rhp_req_t *reqs, const void 
 int rhp_cpu_reply_sessions(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
                            const rhp_session_result_t *results, const uint16_t *route,
                            const rhp_reply_table_t *table, const rhp_reply_out_t *o);
+
+/* rhp_gather_wide (rhp.h) over a speculative batch in host memory after a host
+ * fix-up and rhp_cpu_pack_dense: every pointer of the arguments is host memory,
+ * there is no stream, `work` is not used (it must still be there, as for the
+ * device call).  A sequential walk over the sessions, the totals first and then
+ * the three areas; it shares only the argument check with the kernels.  The
+ * same results for sessions in order and the same -22. */
+int rhp_cpu_gather_wide(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
+                        const rhp_session_result_t *results, const uint64_t *req_start,
+                        const rhp_req_dense_t *dreq, const rhp_http_compact_t *hc, const rhp_wide_out_t *o);
 
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */
 typedef struct rhp_phr_header {

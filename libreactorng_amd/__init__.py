@@ -65,12 +65,13 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 
 # exported C-ABI symbols of librhp.so, as declared in include/rhp.h
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
-               "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions")
+               "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
+               "rhp_gather_wide")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
                 "rhp_cpu_classify_batch", "rhp_emu_fixup_sessions", "rhp_test_fixup_whole", "rhp_test_chunk_window",
-                "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions")
+                "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions", "rhp_cpu_gather_wide")
 
 _rhp = None
 _host = None
@@ -118,6 +119,30 @@ assert SESSION_REPLY_DTYPE.itemsize == 24 and ctypes.sizeof(ReplyTable) == 24 an
 def reply_work_words(n: int, n_sessions: int = 0) -> int:
     """RHP_REPLY_WORK_WORDS (include/rhp.h)"""
     return n + 1 + (n + 63) // 64 + 3 * ((n + 255) // 256)
+
+
+class WideOut(ctypes.Structure):
+    """rhp_wide_out_t (include/rhp.h): the outputs of rhp_gather_wide"""
+    _fields_ = [("totals", ctypes.c_void_p), ("slots", ctypes.c_void_p), ("cap_slots", ctypes.c_uint32),
+                ("hdrs", ctypes.c_void_p), ("cap_hdrs", ctypes.c_uint32), ("body", ctypes.c_void_p),
+                ("cap_body", ctypes.c_uint64), ("work", ctypes.c_void_p)]
+
+
+WIDE_NO_BODY = 0xFFFFFFFFFFFFFFFF
+WIDE_SLOT_DTYPE = np.dtype([("slot", "<u4"), ("hdr_first", "<u4"), ("req", REQ_DTYPE), ("http", HTTP_DTYPE),
+                            ("req_start", "<u8"), ("body_off", "<u8")])
+WIDE_TOTALS_DTYPE = np.dtype([("n_wide", "<u4"), ("n_hdrs", "<u4"), ("body_bytes", "<u8")])
+REQ_DENSE_DTYPE = np.dtype([("ret", "<u2"), ("path_len", "<u2"), ("method_len", "u1"), ("num_headers", "u1"),
+                            ("minor_version", "u1"), ("flags", "u1")])
+HTTP_COMPACT_DTYPE = np.dtype([("result", "i1"), ("body_kind", "u1"), ("flags", "u1"), ("reserved", "u1"),
+                               ("body_len", "<u4")])
+assert WIDE_SLOT_DTYPE.itemsize == 64 and WIDE_TOTALS_DTYPE.itemsize == 16 and ctypes.sizeof(WideOut) == 64
+assert REQ_DENSE_DTYPE.itemsize == 8 and HTTP_COMPACT_DTYPE.itemsize == 8
+
+
+def wide_work_words(n: int) -> int:
+    """RHP_WIDE_WORK_WORDS (include/rhp.h)"""
+    return 5 * ((n + 63) // 64) + 1
 
 
 def _torch_hip_runtime() -> str | None:
@@ -193,6 +218,9 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_reply_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp,
                                             ctypes.POINTER(ReplyTable), ctypes.POINTER(ReplyOut), vp]
         _rhp.rhp_reply_sessions.restype = ctypes.c_int
+        _rhp.rhp_gather_wide.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp, vp, vp,
+                                         ctypes.POINTER(WideOut), vp]
+        _rhp.rhp_gather_wide.restype = ctypes.c_int
     return _rhp
 
 
@@ -243,6 +271,9 @@ def host() -> ctypes.CDLL:
         _host.rhp_cpu_reply_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp,
                                                  ctypes.POINTER(ReplyTable), ctypes.POINTER(ReplyOut)]
         _host.rhp_cpu_reply_sessions.restype = ctypes.c_int
+        _host.rhp_cpu_gather_wide.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp, vp, vp,
+                                              ctypes.POINTER(WideOut)]
+        _host.rhp_cpu_gather_wide.restype = ctypes.c_int
     return _host
 
 
@@ -1323,3 +1354,203 @@ def reply_sessions_gpu(buf, off, sessions, names, routes, resps_for_routes, stat
                       droute.view.cpu().numpy().view(np.uint16)[: db.n])
     finally:
         lib().rhp_set_impl(IMPL_DFA)
+
+
+# ---------------------------------------------------------------------------
+# The wide slots of a round in one area (rhp.h rhp_gather_wide): after the
+# parse, the fix-up and the dense pack, the records of the slots the dense copies
+# cannot hold and the de-framed chunked bodies, in three small contiguous areas.
+
+WIDE_POISON = 0xFF   # what totals, the three areas and work hold before a call (tests)
+
+
+def _wide_out(totals, slots, hdrs, body, work, caps) -> WideOut:
+    """rhp_wide_out_t over numpy arrays or torch tensors; an area whose cap is 0 is NULL"""
+    return WideOut(_addr(totals), _addr(slots) if caps[0] else None, caps[0], _addr(hdrs) if caps[1] else None, caps[1],
+                   _addr(body) if caps[2] else None, caps[2], _addr(work))
+
+
+def _wide_result(totals, slots, hdrs, body, caps):
+    """(totals WIDE_TOTALS_DTYPE scalar, slots WIDE_SLOT_DTYPE [cap_slots], hdrs HDR_DTYPE [cap_hdrs], body u8
+    [cap_body]) from the bytes of the four outputs"""
+    return (totals.view(WIDE_TOTALS_DTYPE)[0], slots[: caps[0] * 64].view(WIDE_SLOT_DTYPE),
+            hdrs[: caps[1] * 8].view(HDR_DTYPE), body[: caps[2]])
+
+
+def gather_wide_cpu(b_or_res, sessions, results, starts, dreq, hc, caps=None, body_shift: int = 0):
+    """rhp_cpu_gather_wide (include/rhp_host.h) over a speculative request-major batch in host memory after a
+    fix-up (the Batch of speculative_cpu or a Result that describes its batch) and its dense pack (dreq, hc of
+    pack_dense_cpu).  caps (cap_slots, cap_hdrs, cap_body); None: the exact ones, from a totals-only call first.
+    Returns (totals, slots [cap_slots], hdrs [cap_hdrs], body [cap_body]): every output held WIDE_POISON before
+    the call.  body_shift: `body` starts that many bytes after a 16-byte boundary."""
+    b = b_or_res.batch if isinstance(b_or_res, Result) else b_or_res
+    if b is None:
+        raise ValueError("this Result does not describe its batch")
+    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
+    results = np.ascontiguousarray(results, dtype=SESSION_RESULT_DTYPE)
+    starts = np.ascontiguousarray(starts, dtype=np.uint64)
+    dreq, hc = np.ascontiguousarray(dreq).view(np.uint8), np.ascontiguousarray(hc).view(np.uint8)
+    work = np.full(wide_work_words(b.n) * 8, WIDE_POISON, dtype=np.uint8)
+
+    def aligned(size, shift=0):
+        raw = np.full(size + shift + 16, WIDE_POISON, dtype=np.uint8)
+        at = (-raw.ctypes.data) % 16 + shift
+        return raw[at: at + size]
+
+    def call(caps):
+        totals, slots, hdrs, body = aligned(16), aligned(caps[0] * 64), aligned(caps[1] * 8), aligned(caps[2], body_shift)
+        o = _wide_out(totals, slots, hdrs, body, work, caps)
+        rc = host().rhp_cpu_gather_wide(ctypes.byref(b), _ptr(sessions), len(sessions), _ptr(results), _ptr(starts),
+                                        _ptr(dreq), _ptr(hc), ctypes.byref(o))
+        if rc != 0:
+            raise RuntimeError(f"rhp_cpu_gather_wide failed: {rc}")
+        return _wide_result(totals, slots, hdrs, body, caps)
+
+    if caps is None:
+        t = call((0, 0, 0))[0]
+        caps = (int(t["n_wide"]), int(t["n_hdrs"]), int(t["body_bytes"]))
+    return call(tuple(int(c) for c in caps))
+
+
+def gather_wide_device(d: Batch, sessions_t, n_sessions: int, results_t, starts_t, dreq_t, hc_t, caps, guard: int = 0,
+                       body_shift: int = 0, stream=None):
+    """One rhp_gather_wide call over device buffers (torch tensors; `d` the parsed, fixed-up and packed batch's
+    descriptor) on the stream (default: the current one).  totals, slots, hdrs, body and work are Guarded (guard
+    bytes on both sides, `body` body_shift bytes into its allocation) and hold WIDE_POISON first.  Returns
+    finish(): synchronize, check the guards, (totals, slots, hdrs, body) as gather_wide_cpu."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    caps = tuple(int(c) for c in caps)
+    g = {"totals": Guarded("totals", 16, guard, fill=WIDE_POISON),
+         "slots": Guarded("slots", max(caps[0] * 64, 1), guard, fill=WIDE_POISON),
+         "hdrs": Guarded("wide hdrs", max(caps[1] * 8, 1), guard, fill=WIDE_POISON),
+         "body": Guarded("body", max(caps[2], 1), guard, fill=WIDE_POISON, shift=body_shift),
+         "work": Guarded("work", wide_work_words(d.n) * 8, guard, fill=WIDE_POISON)}
+    o = _wide_out(*(g[k].view for k in ("totals", "slots", "hdrs", "body", "work")), caps)
+    vp = ctypes.c_void_p
+    rc = lib().rhp_gather_wide(ctypes.byref(d), vp(_addr(sessions_t)), n_sessions, vp(_addr(results_t)), vp(_addr(starts_t)),
+                               vp(_addr(dreq_t)), vp(_addr(hc_t)), ctypes.byref(o), vp(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_gather_wide failed: {rc}")
+
+    def finish(_keep=(sessions_t, results_t, starts_t, dreq_t, hc_t)):
+        torch.cuda.synchronize()
+        if guard:
+            for x in g.values():
+                x.check()
+        return _wide_result(*(g[k].view.cpu().numpy() for k in ("totals", "slots", "hdrs", "body")), caps)
+    return finish
+
+
+def pack_dense_device(db: "DeviceBatch", guard: int = 0):
+    """rhp_pack_dense over the device records of `db` as they are now, on the current stream: the three outputs
+    as Guarded device buffers (dreq 8n, hc 8n, lens16 2 * max_headers * n bytes), holding WIDE_POISON first."""
+    import torch
+    n, m = db.n, db.max_headers
+    outs = [Guarded(name, max(size, 8), guard, fill=WIDE_POISON) for name, size in
+            (("dreq", 8 * n), ("hc", 8 * n), ("lens16", 2 * m * n))]
+    d = db.desc()
+    rc = lib().rhp_pack_dense(ctypes.byref(d), outs[0].view.data_ptr(), outs[1].view.data_ptr(), outs[2].view.data_ptr(),
+                              torch.cuda.current_stream().cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f"rhp_pack_dense failed: {rc}")
+    return outs
+
+
+def gather_wide_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_DFA, caps=None, guard: int = 0,
+                    body_shift: int = 0, details: bool = False):
+    """A round of pipelined input on the GPU up to its one D2H: speculative parse -> rhp_fixup_sessions
+    (fixup_gpu) -> rhp_pack_dense -> rhp_gather_wide.  caps None: the exact ones, from a totals-only call first.
+    Returns (totals, slots, hdrs, body) as gather_wide_cpu; details: also (Result, session results, req_start,
+    dreq u8 [8n], hc u8 [8n], lens16 u16 [max_headers * n]) as the GPU left them."""
+    import torch
+    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
+    res, results, starts, db = fixup_gpu(buf, off, sessions, max_headers, impl, with_batch=True, guard=guard)
+    n, ns = db.n, len(sessions)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda")
+    ds, dres, dst = dev(sessions), dev(results), dev(starts)
+    packed = pack_dense_device(db, guard)
+    d = db.desc()
+
+    def call(caps):
+        return gather_wide_device(d, ds, ns, dres, dst, packed[0].view, packed[1].view, caps, guard, body_shift)()
+
+    if caps is None:
+        t = call((0, 0, 0))[0]
+        caps = (int(t["n_wide"]), int(t["n_hdrs"]), int(t["body_bytes"]))
+    out = call(caps)
+    if guard:
+        db.check_guards()
+        for x in packed:
+            x.check()
+    if not details:
+        return out
+    dreq, hc, lens = (x.view.cpu().numpy() for x in packed)
+    return out + (res, results, starts, dreq[: 8 * n], hc[: 8 * n], lens.view(np.uint16)[: max_headers * n])
+
+
+def rebuild_records(n: int, max_headers: int, sessions, results, dreq, hc, lens16, totals, slots, hdrs, body):
+    """What the reactor holds after one D2H, from the dense copies (dreq, hc, lens16 of rhp_pack_dense), the
+    fix-up's session results and the three gathered areas of rhp_gather_wide alone: a dict with
+      in_use     bool [n]: the record slots the sessions own (rhp.h)
+      wide       bool [n]: the in-use slots found in slots[]
+      reqs       REQ_DTYPE [n], hdrs HDR_DTYPE [n, max_headers], http HTTP_DTYPE [n]: the records of the in-use
+                 slots, the dense ones expanded (rhp_expand_reqs / _records / _http over an RHP_LAYOUT_DENSE
+                 image whose wide areas hold the gathered records), zero elsewhere; of a slot whose http result
+                 is not 1 only that result means anything (rhp.h)
+      req_start  {slot: req_start} of the wide slots
+      bodies     {slot: bytes} of the gathered bodies.
+    The wide slots are visited with a cursor over slots[], which ascend by slot."""
+    m = max_headers
+    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
+    results = np.ascontiguousarray(results, dtype=SESSION_RESULT_DTYPE)
+    dreq = np.ascontiguousarray(dreq).view(np.uint8)[: 8 * n].view(REQ_DENSE_DTYPE).copy()
+    hc = np.ascontiguousarray(hc).view(np.uint8)[: 8 * n].view(HTTP_COMPACT_DTYPE).copy()
+    lens16 = np.ascontiguousarray(lens16).view(np.uint16)[: m * n]
+    nw = int(totals["n_wide"])
+    slots = slots[:nw]
+    in_use = np.zeros(n, dtype=bool)
+    for (lo, hi), k in zip(sessions.tolist(), results["n_slots"].tolist()):
+        if lo + k <= hi <= n:
+            in_use[lo: lo + k] = True
+    # an RHP_LAYOUT_DENSE image of the round: the dense copies, the gathered records in the wide areas
+    raw_reqs = np.zeros(max(reqs_bytes(n, LAYOUT_DENSE), 8), dtype=np.uint8)
+    raw_hdrs = np.zeros(max(hdrs_bytes(n, m, LAYOUT_DENSE), 8), dtype=np.uint8)
+    raw_http = np.zeros(max(http_bytes(n, MODE_HTTP, LAYOUT_DENSE), 8), dtype=np.uint8)
+    wide_reqs = raw_reqs[(n * 8 + 15) & ~15:][: n * 16].view(REQ_DTYPE)
+    wide_hdrs = raw_hdrs[hdrs_bytes(n, m, LAYOUT_DENSE) - n * m * 8:][: n * m * 8].view(HDR_DTYPE).reshape(n, m)
+    wide_http = raw_http[(n * 8 + 15) & ~15:][: n * 24].view(HTTP_DTYPE)
+    wide = np.zeros(n, dtype=bool)
+    req_start, bodies, cursor = {}, {}, 0
+    for i in np.flatnonzero(in_use).tolist():   # the dispatch loop: ascending slots, a cursor over slots[]
+        if cursor < nw and int(slots["slot"][cursor]) == i:
+            w = slots[cursor]
+            cursor += 1
+            wide[i] = True
+            wide_reqs[i], wide_http[i] = w["req"], w["http"]
+            wide_reqs["flags"][i] |= F_WIDE   # (in the dense image: its header records are the wide ones)
+            r, x = w["req"], w["http"]
+            nh = int(r["num_headers"]) if x["result"] == 1 and r["ret"] > 0 and r["num_headers"] <= m else 0
+            wide_hdrs[i, :nh] = hdrs[int(w["hdr_first"]): int(w["hdr_first"]) + nh]
+            req_start[i] = int(w["req_start"])
+            if int(w["body_off"]) != WIDE_NO_BODY:
+                bodies[i] = bytes(body[int(w["body_off"]): int(w["body_off"]) + int(x["body_len"])])
+    assert cursor == nw, "slots[] holds a slot that is not in use, or out of order"
+    # a wide slot reads its records from the wide areas whatever its dense copies say
+    dreq["flags"][wide] = DENSE_WIDE
+    hc["flags"][wide] = HTTP_WIDE
+    dreq[~in_use] = np.zeros((), dtype=REQ_DENSE_DTYPE)
+    dreq["flags"][~in_use] = DENSE_BAD
+    hc[~in_use] = np.zeros((), dtype=HTTP_COMPACT_DTYPE)
+    raw_reqs[: 8 * n] = dreq.view(np.uint8)
+    raw_http[: 8 * n] = hc.view(np.uint8)
+    raw_hdrs[: 2 * m * n] = lens16.view(np.uint8)
+    reqs = expand_reqs(raw_reqs, n, LAYOUT_DENSE)
+    # (a dense request that is not ready -- hc says so -- has no header rows)
+    reqs["num_headers"][(~wide) & (hc["result"] != 1)] = 0
+    out_hdrs = expand_records(reqs, raw_hdrs, n, m, LAYOUT_DENSE)
+    http = expand_http(reqs, raw_http, n, LAYOUT_DENSE)
+    for a in (reqs, out_hdrs, http):
+        a[~in_use] = np.zeros((), dtype=a.dtype)
+    return {"in_use": in_use, "wide": wide, "reqs": reqs, "hdrs": out_hdrs, "http": http, "req_start": req_start,
+            "bodies": bodies}

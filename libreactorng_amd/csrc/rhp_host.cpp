@@ -1,7 +1,7 @@
 /*
  * rhp_host.cpp -- the product's host entry points (rhp_host.h): the exact
  * scalar parser over a batch in host memory, the session fix-up, the dense
- * pack and the three expansions, the host classify and reply, and the pointer-based
+ * pack and the three expansions, the host classify, reply and gather, and the pointer-based
  * rhp_phr_parse_request / rhp_http_read_cpu.  libreactor.so links them.  The
  * parser is rhp_scalar.h's (the code the kernel's rare paths run); where the
  * records sit and how they are encoded is rhp_records.h's.
@@ -16,6 +16,7 @@
 #include "rhp_scalar.h"
 #include "rhp_classify_args.h"
 #include "rhp_reply_args.h"
+#include "rhp_gather_args.h"
 #include "rhp_host_exact.h"
 
 using namespace rhp;
@@ -296,6 +297,67 @@ extern "C" int rhp_cpu_reply_sessions(const rhp_batch_t *b, const rhp_session_t 
       if (len) memcpy(o->out + at, t->images + t->image_off[r], len);
       at += len;
     }
+  }
+  return 0;
+}
+
+/* rhp_gather_wide (rhp.h) on the host, every pointer in host memory: a plain
+ * walk, session by session and slot by slot, twice -- the totals first, then,
+ * when they fit the caps, the records, header records and bodies in the same
+ * order.  With the sessions in order that is ascending slot order.  It shares
+ * the argument check with the kernels' launcher (rhp_gather_args.h) and
+ * nothing else. */
+extern "C" int rhp_cpu_gather_wide(const rhp_batch_t *b, const rhp_session_t *sessions, uint32_t n_sessions,
+                                   const rhp_session_result_t *results, const uint64_t *req_start,
+                                   const rhp_req_dense_t *dreq, const rhp_http_compact_t *hc, const rhp_wide_out_t *o)
+{
+  const int rc = rhp_gather_wide_check(b, sessions, n_sessions, results, req_start, dreq, hc, o);
+  if (rc < 0) return rc;
+  rhp_wide_totals_t tot = {0, 0, 0};
+  if (rc == 1) {
+    *o->totals = tot;
+    return 0;
+  }
+  const uint32_t n = b->n, m = b->max_headers;
+  const uint8_t *bytes = b->bytes_rw ? b->bytes_rw : b->bytes;
+  for (int pass = 0; pass < 2; pass++) {
+    uint64_t at_slot = 0, at_hdr = 0, at_body = 0;
+    for (uint32_t s = 0; s < n_sessions; s++) {
+      const uint32_t lo = sessions[s].piece_lo, hi = sessions[s].piece_hi, ns = results[s].n_slots;
+      if (!((uint64_t) lo + ns <= hi && hi <= n)) continue;   /* owns nothing */
+      for (uint32_t i = lo; i < lo + ns; i++) {
+        const bool hw = hc[i].flags & RHP_HTTP_WIDE;
+        if (!hw && !(hc[i].result == 1 && (dreq[i].flags & RHP_DENSE_WIDE))) continue;
+        const rhp_req_t &r = b->reqs[i];
+        const rhp_http_t &x = b->http[i];
+        const uint32_t nh = x.result == 1 && r.ret > 0 && r.num_headers <= m ? r.num_headers : 0u;
+        const uint64_t from = req_start[i] + (uint64_t) (int64_t) r.ret;
+        bool body = x.result == 1 && x.body_kind == 1u && x.consumed != (uint64_t) (int64_t) r.ret + x.body_len;
+        body = body && b->offsets[lo] <= from && from <= b->offsets[hi] && x.body_len <= b->offsets[hi] - from;
+        if (pass) {
+          rhp_wide_slot_t w;
+          w.slot = i;
+          w.hdr_first = (uint32_t) at_hdr;
+          w.req = r;
+          w.http = x;
+          w.req_start = req_start[i];
+          w.body_off = body ? at_body : RHP_WIDE_NO_BODY;
+          o->slots[at_slot] = w;
+          if (nh) memcpy(o->hdrs + at_hdr, b->hdrs + (uint64_t) i * m, sizeof(rhp_hdr_t) * nh);
+          if (body && x.body_len) memcpy(o->body + at_body, bytes + from, x.body_len);
+        }
+        at_slot++;
+        at_hdr += nh;
+        if (body) at_body += x.body_len;
+      }
+    }
+    if (pass) break;
+    tot.n_wide = (uint32_t) (at_slot < 0xffffffffull ? at_slot : 0xffffffffull);
+    tot.n_hdrs = (uint32_t) (at_hdr < 0xffffffffull ? at_hdr : 0xffffffffull);
+    tot.body_bytes = at_body;
+    *o->totals = tot;
+    /* (sessions that overlap, against the contract, may count a slot twice: the saturated counts fit no area) */
+    if (at_slot > o->cap_slots || at_hdr > o->cap_hdrs || at_body > o->cap_body) break;   /* totals only */
   }
   return 0;
 }
