@@ -21,10 +21,12 @@
  *
  * rhp_classify_sessions (rhp.h) is the same lookup over the record slots
  * rhp_fixup_sessions leaves in a speculative batch: one slot per lane, the
- * slot's session by binary search over sessions[].piece_lo, the request's
- * first byte from req_start[i].  Its kernel restates the first one's table load,
- * compare, absent fill and route match; stating them once is deferred (DESIGN
- * 3.5).  The launchers share fill_params.
+ * slot's session by binary search over sessions[].piece_lo (sessions_upto,
+ * rhp_device.h, shared with rhp_reply.hip and rhp_gather.hip), the request's
+ * first byte from req_start[i].  Its kernel writes out the first one's table
+ * load, compare, absent fill and route match again: the forms of stating them
+ * once that were tried, and why none is here, are in DESIGN 3.5.  The launchers
+ * share fill_params.
  */
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -33,6 +35,7 @@
 
 #include "rhp.h"
 #include "rhp_classify_args.h"
+#include "rhp_device.h"
 
 namespace {
 
@@ -312,11 +315,7 @@ __global__ __launch_bounds__(256) void rhp_classify_sessions_kernel(SParams p)
   if (i >= n) return;
 
   /* ---- the slot's session: the sessions before `above` have piece_lo <= i ---- */
-  uint32_t above = 0;
-  for (uint32_t hi = p.n_sessions; above < hi;) {
-    const uint32_t mid = above + ((hi - above) >> 1);
-    if (p.sessions[mid].piece_lo <= i) above = mid + 1u; else hi = mid;
-  }
+  const uint32_t above = rhp_device::sessions_upto(p.sessions, p.n_sessions, i);
 
   /* ---- in use?  ready?  then the request record and the request's first byte ---- */
   int32_t ret = 0;
@@ -326,7 +325,11 @@ __global__ __launch_bounds__(256) void rhp_classify_sessions_kernel(SParams p)
   if (above) {
     const uint2 se = reinterpret_cast<const uint2 *>(p.sessions)[above - 1u];   /* piece_lo, piece_hi */
     const uint32_t n_slots = p.results[above - 1u].n_slots;
-    /* (se.y <= n: offsets[piece_hi] is an entry of offsets) */
+    /* (se.y <= n: offsets[piece_hi] is an entry of offsets).  Not rhp_device.h's
+     * in_use(): this test asks se.x <= se.y where that one asks se.x + n_slots <=
+     * se.y, so a session whose n_slots passes piece_hi is classified here and not
+     * answered or gathered there.  The difference is known; this test and the host
+     * twin's define what rhp_classify_sessions returns, and it stays as it is */
     if (se.x <= i && i - se.x < n_slots && se.x <= se.y && se.y <= n &&
         *reinterpret_cast<const int32_t *>(p.http + (size_t) i * sizeof(rhp_http_t)) == 1) {
       const uint4 q = reinterpret_cast<const uint4 *>(p.reqs)[i];

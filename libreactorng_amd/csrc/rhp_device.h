@@ -1,0 +1,111 @@
+/*
+ * rhp_device.h -- the device helpers that more than one of rhp_writer.hip,
+ * rhp_classify.hip, rhp_reply.hip and rhp_gather.hip use, stated once: the
+ * inclusive scan of a wave, the wave's copy of a byte range, the flush of a
+ * wave's LDS stage, and the search and the test that give a record slot its
+ * session.  Device code only; every function is inlined into its caller.
+ */
+#ifndef RHP_DEVICE_H
+#define RHP_DEVICE_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rhp.h"
+
+namespace rhp_device {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) uint8_t lds8;
+typedef __attribute__((address_space(3))) uint32_t lds32;
+
+/* inclusive sum over the wave's 64 lanes (unsigned long long or uint32_t) */
+template <class T>
+__device__ __forceinline__ T wave_incl_scan(T v, uint32_t lane)
+{
+  for (int o = 1; o < 64; o <<= 1) {
+    const T u = __shfl_up(v, o);
+    if ((int) lane >= o) v += u;
+  }
+  return v;
+}
+
+/* d[0, len) <- src[0, len) across the wave, all 64 lanes calling: bytes up to
+ * the first 16-aligned destination, then 16 bytes per lane (1 KiB per store
+ * instruction) from funnel-shifted aligned source dwords, then the tail bytes;
+ * below 128 bytes a byte per lane.  The read contract: no byte outside the
+ * aligned dwords that hold [src, src + len) is read -- the dword past the
+ * last one a 16-byte step needs is loaded only if the range reaches it */
+__device__ __forceinline__ void put(uint8_t *d, const uint8_t *src, uint64_t len, uint32_t lane)
+{
+  if (len < 128) {
+    for (uint32_t j = lane; j < len; j += 64) d[j] = src[j];
+    return;
+  }
+  const uint32_t head = (uint32_t) ((16u - ((uintptr_t) d & 15u)) & 15u);
+  if (lane < head) d[lane] = src[lane];
+  const uint8_t *s = src + head;
+  const uint64_t body = (len - head) & ~(uint64_t) 15u;
+  const uintptr_t sa = (uintptr_t) s;
+  const uint32_t *w = reinterpret_cast<const uint32_t *>(sa & ~(uintptr_t) 3);
+  const uint32_t sh = (uint32_t) sa & 3u;
+  const uint64_t nd = (sh + (len - head) + 3u) >> 2;
+  for (uint64_t j = 16u * lane; j < body; j += 1024u) {
+    const uint64_t k = j >> 2;
+    const uint32_t w0 = w[k], w1 = w[k + 1], w2 = w[k + 2], w3 = w[k + 3], w4 = k + 4 < nd ? w[k + 4] : 0u;
+    *reinterpret_cast<u32x4 *>(d + head + j) = u32x4{__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
+                                                     __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh)};
+  }
+  for (uint64_t j = head + body + lane; j < len; j += 64) d[j] = src[j];
+}
+
+/* out[G0, G1) <- stage[shift, shift + G1 - G0), the wave's LDS stage L that its
+ * lanes have just written, shift = (out + G0) & 15 so that LDS and HBM agree
+ * modulo 16: 16-byte stores between the first and the last 16-aligned
+ * addresses, byte stores outside.  All 64 lanes call it; the stage may be
+ * written again when it returns */
+__device__ __forceinline__ void flush_stage(const lds8 *L, uint32_t shift, uint8_t *out, uint64_t G0, uint64_t G1, uint32_t lane)
+{
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_s_waitcnt(0xc07f);   /* lgkmcnt(0): the stage is written (wave-local) */
+  __builtin_amdgcn_wave_barrier();
+  const uint64_t A0 = G0 + ((16u - shift) & 15u), A1 = G1 - (((uint32_t) (uintptr_t) (out + G1)) & 15u);
+  if (A0 < A1) {
+    for (uint64_t a = A0 + 16u * lane; a < A1; a += 1024u) {
+      const uint32_t so = (uint32_t) (a - G0) + shift;
+      const u32x4 d = *reinterpret_cast<const __attribute__((address_space(3))) u32x4 *>(L + so);
+      *reinterpret_cast<u32x4 *>(out + a) = d;
+    }
+    if (lane < A0 - G0) out[G0 + lane] = L[shift + lane];
+    if (lane < G1 - A1) out[A1 + lane] = L[shift + (uint32_t) (A1 - G0) + lane];
+  } else {   /* the whole range within one 16-byte line (or two) */
+    for (uint32_t j = lane; j < G1 - G0; j += 64) out[G0 + j] = L[shift + j];
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+/* the number of sessions whose piece_lo <= i (bisection; sessions ascend by
+ * piece_lo, rhp.h: the owner of slot i is the last of them) */
+__device__ __forceinline__ uint32_t sessions_upto(const rhp_session_t *sessions, uint32_t n_sessions, uint32_t i)
+{
+  uint32_t above = 0;
+  for (uint32_t hi = n_sessions; above < hi;) {
+    const uint32_t mid = above + ((hi - above) >> 1);
+    if (sessions[mid].piece_lo <= i) above = mid + 1u; else hi = mid;
+  }
+  return above;
+}
+
+/* the one test that lets a load of slot i's records through, whatever the
+ * search returned: the session's fields (piece_lo, piece_hi, n_slots) hold in
+ * a batch of n slots and contain i.  (n by reference: the callers pass a member
+ * of their kernel argument, read where the test comes to it, which keeps
+ * rhp_gather.hip's kernels the instruction streams they were) */
+__device__ __forceinline__ bool in_use(uint32_t i, uint32_t lo, uint32_t hi, uint32_t ns, const uint32_t &n)
+{
+  return lo <= i && i - lo < ns && (uint64_t) lo + ns <= hi && hi <= n;
+}
+
+}  // namespace rhp_device
+
+#endif

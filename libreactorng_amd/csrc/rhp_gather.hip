@@ -25,9 +25,10 @@
  *                           records (a lane per record) and each body (put():
  *                           16 bytes per lane, bytes at the two edges)
  *
- * The session search is rhp_classify_sessions_kernel's bisection, restated,
- * per marked lane; the session's fields as loaded must contain the slot before
- * anything of the slot's records is read (in_use()).  A search once per wave
+ * The session search is rhp_classify_sessions_kernel's bisection
+ * (sessions_upto, rhp_device.h), per marked lane; the session's fields as
+ * loaded must contain the slot before anything of the slot's records is read
+ * (in_use(), rhp_device.h).  A search once per wave
  * (a 64-way search for the wave's first slot, 64 sessions from there in LDS, a
  * bisection in LDS per lane) was built and measured: it was no faster at any
  * round size and 3 % slower with 65536 sessions, so it is not here.
@@ -36,17 +37,20 @@
  * still a prefix sum of the lengths that are copied, the copy runs only when
  * the totals fit the caps, and the copy kernel takes its lengths from the same
  * records and masks as the sums: nothing is written outside [0, cap) of an
- * area.  put() restates rhp_reply.hip's (that file is not edited here; stating
- * it once is deferred).
+ * area.  put() is rhp_device.h's too, shared with rhp_reply.hip and
+ * rhp_writer.hip.
  */
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "rhp.h"
+#include "rhp_device.h"
 #include "rhp_gather_args.h"
 
 namespace {
+
+using namespace rhp_device;
 
 struct GParams {
   const uint8_t              *bytes;     /* bytes_rw when set */
@@ -72,23 +76,6 @@ struct GParams {
 constexpr uint32_t kTopThreads = 1024;
 constexpr uint32_t kTopSlots = kTopThreads * 64u;   /* above it rhp_gather_top_kernel gives a thread more than one wave's sums */
 
-/* the number of sessions whose piece_lo <= i (bisection; in order: the owner is the last of them) */
-__device__ __forceinline__ uint32_t sessions_upto(const GParams &p, uint32_t i)
-{
-  uint32_t above = 0;
-  for (uint32_t hi = p.n_sessions; above < hi;) {
-    const uint32_t mid = above + ((hi - above) >> 1);
-    if (p.sessions[mid].piece_lo <= i) above = mid + 1u; else hi = mid;
-  }
-  return above;
-}
-
-/* the one test that lets a load of slot i's records through: the session's fields hold and contain i */
-__device__ __forceinline__ bool in_use(const GParams &p, uint32_t i, uint32_t lo, uint32_t hi, uint32_t ns)
-{
-  return lo <= i && i - lo < ns && (uint64_t) lo + ns <= hi && hi <= p.n;
-}
-
 struct Owner {
   bool     ok;
   uint32_t lo, hi;   /* piece_lo, piece_hi */
@@ -97,10 +84,10 @@ struct Owner {
 /* the session that owns slot i: the last whose piece_lo <= i, when its fields contain i */
 __device__ __forceinline__ Owner owner_of(const GParams &p, uint32_t i)
 {
-  const uint32_t above = sessions_upto(p, i);
+  const uint32_t above = sessions_upto(p.sessions, p.n_sessions, i);
   if (!above) return Owner{false, 0, 0};
   const uint2 se = reinterpret_cast<const uint2 *>(p.sessions)[above - 1u];
-  return Owner{in_use(p, i, se.x, se.y, p.results[above - 1u].n_slots), se.x, se.y};
+  return Owner{in_use(i, se.x, se.y, p.results[above - 1u].n_slots, p.n), se.x, se.y};
 }
 
 /* the wide marks of slot i < n (rhp.h): hc.flags & RHP_HTTP_WIDE, or hc.result == 1 and dreq.flags & RHP_DENSE_WIDE */
@@ -188,35 +175,6 @@ __global__ __launch_bounds__(kTopThreads) void rhp_gather_top_kernel(GParams p)
   }
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-/* one body across the wave (rhp_reply.hip's put): bytes up to the first
- * 16-aligned destination, then 16 bytes per lane from funnel-shifted aligned
- * source dwords, then the tail bytes.  No byte outside the dwords that hold
- * [src, src + len) is read */
-__device__ __forceinline__ void put(uint8_t *d, const uint8_t *src, uint64_t len, uint32_t lane)
-{
-  if (len < 128) {
-    for (uint32_t j = lane; j < len; j += 64) d[j] = src[j];
-    return;
-  }
-  const uint32_t head = (uint32_t) ((16u - ((uintptr_t) d & 15u)) & 15u);
-  if (lane < head) d[lane] = src[lane];
-  const uint8_t *s = src + head;
-  const uint64_t body = (len - head) & ~(uint64_t) 15u;
-  const uintptr_t sa = (uintptr_t) s;
-  const uint32_t *w = reinterpret_cast<const uint32_t *>(sa & ~(uintptr_t) 3);
-  const uint32_t sh = (uint32_t) sa & 3u;
-  const uint64_t nd = (sh + (len - head) + 3u) >> 2;
-  for (uint64_t j = 16u * lane; j < body; j += 1024u) {
-    const uint64_t k = j >> 2;
-    const uint32_t w0 = w[k], w1 = w[k + 1], w2 = w[k + 2], w3 = w[k + 3], w4 = k + 4 < nd ? w[k + 4] : 0u;
-    *reinterpret_cast<u32x4 *>(d + head + j) = u32x4{__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
-                                                     __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh)};
-  }
-  for (uint64_t j = head + body + lane; j < len; j += 64) d[j] = src[j];
-}
-
 __global__ __launch_bounds__(256) void rhp_gather_copy_kernel(GParams p)
 {
   const uint32_t lane = threadIdx.x & 63u;
@@ -240,6 +198,7 @@ __global__ __launch_bounds__(256) void rhp_gather_copy_kernel(GParams p)
   }
   const uint32_t nh = wide ? n_hdrs(p, r, x) : 0u;
   const unsigned long long bl = has_body ? x.body_len : 0;
+  /* (two sums in one loop: as two calls of wave_incl_scan the call measured 0.7 % slower at 65536 slots) */
   uint32_t hinc = nh;
   unsigned long long binc = bl;
   for (int o = 1; o < 64; o <<= 1) {

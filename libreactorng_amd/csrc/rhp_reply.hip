@@ -8,7 +8,8 @@
  *
  * One record slot per lane.  A slot is live when it is in use by a session
  * whose fields hold and whose walk did not stop on -1, and its route is
- * static; its session comes from the search rhp_classify_sessions_kernel does.
+ * static; its session comes from the search rhp_classify_sessions_kernel does
+ * (sessions_upto, rhp_device.h).
  * A slot is answered when every slot from its session's piece_lo up to it is
  * live.  Inside a wave that is bit arithmetic on the ballot of the live flags;
  * only a run that began before the wave's first slot depends on what came
@@ -39,17 +40,21 @@
  *
  * Whatever the searches return, an offset is a prefix sum of the lengths that
  * are copied and *total bounds them all, so sessions in any order write nothing
- * outside out[0, total).  put() and the stage's flush restate rhp_writer.hip's
- * (that file is not edited here; stating them once is deferred).
+ * outside out[0, total).  The session search and the in-use test, the wave's
+ * scan, put() and the stage's flush are rhp_device.h's, shared with
+ * rhp_classify.hip, rhp_gather.hip and rhp_writer.hip.
  */
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "rhp.h"
+#include "rhp_device.h"
 #include "rhp_reply_args.h"
 
 namespace {
+
+using namespace rhp_device;
 
 struct RParams {
   const uint8_t              *http;
@@ -92,19 +97,14 @@ __device__ __forceinline__ Agg combine(const Agg &a, const Agg &b)
   return r;
 }
 
-/* slot i < n: kLive | route << 32 | piece_lo when it is live, else 0.  The search
- * and the test that lets a load through are rhp_classify_sessions_kernel's */
+/* slot i < n: kLive | route << 32 | piece_lo when it is live, else 0 */
 __device__ __forceinline__ uint64_t slot_info(const RParams &p, uint32_t i)
 {
-  uint32_t above = 0;
-  for (uint32_t hi = p.n_sessions; above < hi;) {
-    const uint32_t mid = above + ((hi - above) >> 1);
-    if (p.sessions[mid].piece_lo <= i) above = mid + 1u; else hi = mid;
-  }
+  const uint32_t above = sessions_upto(p.sessions, p.n_sessions, i);
   if (!above) return 0;
   const uint2 se = reinterpret_cast<const uint2 *>(p.sessions)[above - 1u];   /* piece_lo, piece_hi */
   const uint32_t ns = p.results[above - 1u].n_slots;
-  if (!(se.x <= i && i - se.x < ns && (uint64_t) se.x + ns <= se.y && se.y <= p.n)) return 0;
+  if (!in_use(i, se.x, se.y, ns, p.n)) return 0;
   /* the walk's last slot (piece_lo + n_slots - 1 < piece_hi <= n): stopped on -1? */
   if (*reinterpret_cast<const int32_t *>(p.http + (size_t) (se.x + ns - 1u) * sizeof(rhp_http_t)) == -1) return 0;
   const uint32_t r = p.route[i];
@@ -221,45 +221,10 @@ __global__ __launch_bounds__(256) void rhp_reply_scan_kernel(RParams p)
   }
   const bool answered = w.ok && (!w.cond || x);
   const unsigned long long v = answered ? w.len : 0;
-  unsigned long long inc = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long u = __shfl_up(inc, o);
-    if ((int) lane >= o) inc += u;
-  }
+  const unsigned long long inc = wave_incl_scan(v, lane);
   const uint64_t m = __ballot(answered);
   if (i < p.n) p.pos[i] = off + inc - v;
   if (lane == 0 && i < p.n) p.mask[i >> 6] = m;
-}
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) uint8_t lds8;
-typedef __attribute__((address_space(3))) uint32_t lds32;
-
-/* one image across the wave (rhp_writer.hip's put): bytes up to the first
- * 16-aligned destination, then 16 bytes per lane from funnel-shifted aligned
- * source dwords, then the tail bytes.  No byte outside the dwords that hold
- * [src, src + len) is read */
-__device__ __forceinline__ void put(uint8_t *d, const uint8_t *src, uint64_t len, uint32_t lane)
-{
-  if (len < 128) {
-    for (uint32_t j = lane; j < len; j += 64) d[j] = src[j];
-    return;
-  }
-  const uint32_t head = (uint32_t) ((16u - ((uintptr_t) d & 15u)) & 15u);
-  if (lane < head) d[lane] = src[lane];
-  const uint8_t *s = src + head;
-  const uint64_t body = (len - head) & ~(uint64_t) 15u;
-  const uintptr_t sa = (uintptr_t) s;
-  const uint32_t *w = reinterpret_cast<const uint32_t *>(sa & ~(uintptr_t) 3);
-  const uint32_t sh = (uint32_t) sa & 3u;
-  const uint64_t nd = (sh + (len - head) + 3u) >> 2;
-  for (uint64_t j = 16u * lane; j < body; j += 1024u) {
-    const uint64_t k = j >> 2;
-    const uint32_t w0 = w[k], w1 = w[k + 1], w2 = w[k + 2], w3 = w[k + 3], w4 = k + 4 < nd ? w[k + 4] : 0u;
-    *reinterpret_cast<u32x4 *>(d + head + j) = u32x4{__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
-                                                     __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh)};
-  }
-  for (uint64_t j = head + body + lane; j < len; j += 64) d[j] = src[j];
 }
 
 /* one image by one lane into its wave's stage at byte o: aligned LDS dwords,
@@ -348,24 +313,7 @@ __global__ __launch_bounds__(256) void rhp_reply_copy_kernel(RParams p)
       continue;
     }
     lds_put(L, shift + (uint32_t) (at - G0), p.images + from, (uint32_t) len);
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xc07f);   /* lgkmcnt(0): the stage is written (wave-local) */
-    __builtin_amdgcn_wave_barrier();
-    /* out[G0, G1) <- stage[shift, shift + G1 - G0): 16-byte stores between the
-     * first and the last 16-aligned addresses, byte stores outside */
-    const uint64_t A0 = G0 + ((16u - shift) & 15u), A1 = G1 - (((uint32_t) (uintptr_t) (p.out + G1)) & 15u);
-    if (A0 < A1) {
-      for (uint64_t a = A0 + 16u * lane; a < A1; a += 1024u) {
-        const uint32_t so = (uint32_t) (a - G0) + shift;
-        const u32x4 d = *reinterpret_cast<const __attribute__((address_space(3))) u32x4 *>(L + so);
-        *reinterpret_cast<u32x4 *>(p.out + a) = d;
-      }
-      if (lane < A0 - G0) p.out[G0 + lane] = L[shift + lane];
-      if (lane < G1 - A1) p.out[A1 + lane] = L[shift + (uint32_t) (A1 - G0) + lane];
-    } else {   /* the whole run within one 16-byte line (or two) */
-      for (uint32_t j = lane; j < G1 - G0; j += 64) p.out[G0 + j] = L[shift + j];
-    }
-    __builtin_amdgcn_wave_barrier();
+    flush_stage(L, shift, p.out, G0, G1, lane);
   }
 }
 

@@ -25,6 +25,8 @@
  *                          bodies) is written response by response, the wave's 64
  *                          lanes copying each segment
  *
+ * The wave's scan, its copy of a segment (put) and the stage's flush are
+ * rhp_device.h's, shared with rhp_reply.hip and rhp_gather.hip.
  * Byte copies are HBM-bound; the response bytes written are the algorithmic bytes.
  */
 #include <hip/hip_runtime.h>
@@ -33,8 +35,11 @@
 #include <string.h>
 
 #include "rhp.h"
+#include "rhp_device.h"
 
 namespace {
+
+using namespace rhp_device;
 
 struct WParams {
   const uint8_t *arena;
@@ -84,15 +89,6 @@ __device__ __forceinline__ uint64_t resp_size(const WParams &p, const rhp_resp_t
  * coalesced; within a workgroup a thread scans 4 consecutive sizes, a wave its
  * 64 threads through shuffles, the workgroup its 16 waves through LDS. */
 constexpr uint32_t kTile = 4096;   /* 1024 threads x 4 */
-
-__device__ __forceinline__ unsigned long long wave_incl_scan(unsigned long long v, uint32_t lane)
-{
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long u = __shfl_up(v, o);
-    if ((int) lane >= o) v += u;
-  }
-  return v;
-}
 
 /* inclusive scan of one value per thread over a 1024-thread workgroup */
 __device__ __forceinline__ unsigned long long block_incl_scan(unsigned long long v, unsigned long long *part)
@@ -164,33 +160,10 @@ __global__ __launch_bounds__(1024) void rhp_resp_tile_scan_kernel(uint64_t *a, u
   if (blockIdx.x == 0 && threadIdx.x == 0) a[0] = 0;
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-/* one segment of a response: bytes up to the first 16-aligned destination,
- * then 16 bytes per lane (1 KiB per store instruction) from funnel-shifted
- * aligned source dwords, then the tail bytes */
+/* one segment of a response across the wave (rhp_device.h), o advancing past it */
 __device__ __forceinline__ void put(uint8_t *dst, uint64_t &o, const uint8_t *src, uint32_t len, uint32_t lane)
 {
-  uint8_t *d = dst + o;
-  const uint32_t head = min(len, (uint32_t) ((16u - ((uintptr_t) d & 15u)) & 15u));
-  if (len < 128) {
-    for (uint32_t j = lane; j < len; j += 64) d[j] = src[j];
-    o += len;
-    return;
-  }
-  if (lane < head) d[lane] = src[lane];
-  const uint8_t *s = src + head;
-  const uint32_t body = (len - head) & ~15u;
-  const uintptr_t sa = (uintptr_t) s;
-  const uint32_t *w = reinterpret_cast<const uint32_t *>(sa & ~(uintptr_t) 3);
-  const uint32_t sh = (uint32_t) sa & 3u, nd = (sh + (len - head) + 3u) >> 2;
-  for (uint32_t j = 16u * lane; j < body; j += 1024u) {
-    const uint32_t k = j >> 2;
-    const uint32_t w0 = w[k], w1 = w[k + 1], w2 = w[k + 2], w3 = w[k + 3], w4 = k + 4 < nd ? w[k + 4] : 0u;
-    *reinterpret_cast<u32x4 *>(d + head + j) = u32x4{__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
-                                                     __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh)};
-  }
-  for (uint32_t j = head + body + lane; j < len; j += 64) d[j] = src[j];
+  rhp_device::put(dst + o, src, len, lane);
   o += len;
 }
 __device__ __forceinline__ void put_c(uint8_t *dst, uint64_t &o, const char *src, uint32_t len, uint32_t lane)
@@ -230,8 +203,6 @@ __device__ void write_one(const WParams &p, uint32_t i, uint32_t lane)
 }
 
 /* ---- the lane-per-response stage writers (LDS byte o of the wave's stage) ---- */
-typedef __attribute__((address_space(3))) uint8_t lds8;
-
 /* a compile-time constant string */
 template <uint32_t N>
 __device__ __forceinline__ void st_const(lds8 *L, uint32_t &o, const char (&s)[N])
@@ -306,24 +277,7 @@ __global__ __launch_bounds__(256) void rhp_resp_write_kernel(WParams p)
       st_const(L, o, "\r\n");   /* the empty line */
       st_span(L, o, p.arena + r.body.off, r.body.len);
     }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xc07f);   /* lgkmcnt(0): the stage is written (wave-local) */
-    __builtin_amdgcn_wave_barrier();
-    /* out[G0, G1) <- stage[shift, shift + G1 - G0): 16-byte stores between the
-     * first and the last 16-aligned addresses, byte stores outside */
-    const uint64_t A0 = G0 + ((16u - shift) & 15u), A1 = G1 - (((uint32_t) (uintptr_t) (p.out + G1)) & 15u);
-    if (A0 < A1) {
-      for (uint64_t a = A0 + 16u * lane; a < A1; a += 1024u) {
-        const uint32_t so = (uint32_t) (a - G0) + shift;
-        const u32x4 d = *reinterpret_cast<const __attribute__((address_space(3))) u32x4 *>(L + so);
-        *reinterpret_cast<u32x4 *>(p.out + a) = d;
-      }
-      if (lane < A0 - G0) p.out[G0 + lane] = L[shift + lane];
-      if (lane < G1 - A1) p.out[A1 + lane] = L[shift + (uint32_t) (A1 - G0) + lane];
-    } else {   /* the whole group within one 16-byte line (or two) */
-      for (uint32_t j = lane; j < G1 - G0; j += 64) p.out[G0 + j] = L[shift + j];
-    }
-    __builtin_amdgcn_wave_barrier();
+    flush_stage(L, shift, p.out, G0, G1, lane);
   }
 }
 
