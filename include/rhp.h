@@ -238,7 +238,9 @@ int rhp_parse_batch(const rhp_batch_t *batch, void *stream);
  * A session's unconsumed input is split by the caller at every empty line (the
  * end of a header section: LF LF or LF CR LF) into pieces that are consecutive
  * requests of a RHP_BATCH_SPECULATIVE http batch, so every request's header
- * section ends a piece (#pieces >= #requests).  After rhp_parse_batch,
+ * section ends a piece (#pieces >= #requests); rhp_split_sessions (below) is
+ * that split on the device, from the sessions' packed bytes to offsets[] and
+ * rhp_session_t[].  After rhp_parse_batch,
  * rhp_fixup_sessions walks each session in order, as http_read_request would be
  * called in a loop over the whole input: a piece that starts at the next request
  * boundary and whose result cannot change with more input (1 within the piece,
@@ -636,6 +638,72 @@ int rhp_gather_wide(const rhp_batch_t *batch, const rhp_session_t *sessions, uin
                     const rhp_session_result_t *results, const uint64_t *req_start,
                     const rhp_req_dense_t *dreq, const rhp_http_compact_t *hc,
                     const rhp_wide_out_t *o, void *stream);
+
+/*
+ * The split in front of the parse, on the device: the packed input of a
+ * round's sessions cut at every empty line into the pieces of a
+ * RHP_BATCH_SPECULATIVE batch (offsets[]) and the sessions' piece ranges
+ * (rhp_session_t[]), as rhp_fixup_sessions documents the split above.
+ *   Session s is bytes[sess_off[s], sess_off[s+1]), a = sess_off[s], e =
+ *   sess_off[s+1]: the sessions lie back to back.  sess_off (device
+ *   [n_sessions + 1]) is non-decreasing, sess_off[0] may be non-zero and
+ *   sess_off[n_sessions] <= bytes_end; bytes_end is the host's copy of the packed
+ *   length and sizes the launch.
+ *   Cut.  An absolute position p, a < p < e, is a cut when bytes[p-1] == LF and
+ *   either p-2 >= a && bytes[p-2] == LF, or p-3 >= a && bytes[p-2] == CR &&
+ *   bytes[p-3] == LF: the look-back never crosses the session's start.  p == a and
+ *   p == e are never cuts (an empty line that ends the input makes no empty
+ *   piece); overlapping empty lines each cut (LF LF LF x: at 2 and at 3).
+ *   Pieces.  Session s has 1 + cuts(s) pieces, an empty session one empty piece:
+ *   *n_pieces = n_sessions + the cuts of all sessions.  sessions[s].piece_lo = s +
+ *   (the cuts at positions < a), piece_hi = piece_lo + 1 + cuts(s);
+ *   offsets[piece_lo(s)] = a; the j-th cut over all sessions (ascending position,
+ *   from 0), lying in session s, is offsets[s + j + 1]; offsets[k] =
+ *   sess_off[n_sessions] for n_pieces <= k <= cap_pieces.
+ *   The tail fill lets the caller go on without a host step: rhp_parse_batch
+ *   with n = cap_pieces and RHP_BATCH_SPECULATIVE over these offsets (the
+ *   trailing pieces are empty, no session owns them, and every *_sessions call
+ *   treats such slots as not in use).
+ *   Overflow.  When *n_pieces > cap_pieces nothing is written to offsets or
+ *   sessions; *n_pieces is always written and exact (grow and call again, as
+ *   rhp_write_responses and rhp_gather_wide).  A caller who launches the parse
+ *   without reading *n_pieces first either holds cap_pieces >= n_sessions +
+ *   sess_off[n_sessions] - sess_off[0] (no input has more pieces) or zeroes
+ *   offsets and sessions before the call (every piece empty, no session owns one).
+ *   n_sessions == 0: *n_pieces = 0, offsets[0 .. cap_pieces] = sess_off[0].
+ * Memory.  `bytes` is 16-byte aligned (as rhp_batch_t.bytes) and is read only as
+ * the aligned 16-byte groups that hold [sess_off[0], sess_off[n_sessions]).  With
+ * sess_off not monotone the answers are unspecified; still nothing is read
+ * outside bytes[0, bytes_end) rounded out to 16 bytes and sess_off, and nothing
+ * is written outside n_pieces, work, offsets[0, cap_pieces] and
+ * sessions[0, n_sessions).
+ * -EINVAL: a NULL sess_off, o, n_pieces, offsets or work; a NULL sessions with
+ * n_sessions > 0; a NULL or misaligned bytes with bytes_end > 0; bytes_end +
+ * n_sessions >= 2^32.
+ * Launch contract as rhp_gather_wide: asynchronous on `stream`, no allocation,
+ * no copy, no host synchronisation; thread-safe.  Three launches (a wave's cut
+ * masks and count per RHP_SPLIT_STEP_BYTES of input, one workgroup's scan of the
+ * counts with *n_pieces, the offsets and sessions with the tail fill); two when
+ * bytes_end == 0.
+ */
+#define RHP_SPLIT_STEP_BYTES 1024u   /* what one wave marks: 64 lanes x 16 bytes */
+
+typedef struct rhp_split_out {
+  uint64_t      *n_pieces;   /* device [1]: always written, exact */
+  uint64_t      *offsets;    /* device [cap_pieces + 1] */
+  uint32_t       cap_pieces;
+  rhp_session_t *sessions;   /* device [n_sessions] */
+  uint64_t      *work;       /* device scratch, >= RHP_SPLIT_WORK_WORDS(bytes_end, n_sessions) u64 */
+} rhp_split_out_t;
+
+/* per step: 16 cut masks (a u64 per 64 bytes), 16 u32 counts of the cuts before each mask inside its step, the
+ * step's count; one word for the total */
+#define RHP_SPLIT_WORK_WORDS(bytes_end, n_sessions) \
+  (25u * (((uint64_t) (bytes_end) + RHP_SPLIT_STEP_BYTES - 1u) / RHP_SPLIT_STEP_BYTES) + 1u + 0u * (uint64_t) (n_sessions))
+
+int rhp_split_sessions(const uint8_t *bytes, uint64_t bytes_end,
+                       const uint64_t *sess_off /* device [n_sessions + 1] */, uint32_t n_sessions,
+                       const rhp_split_out_t *o, void *stream);
 
 
 #ifdef __cplusplus

@@ -25,6 +25,7 @@
  *                         host fix-up left in a speculative batch
  *   rhp_cpu_reply_sessions, rhp_cpu_gather_wide  rhp_reply_sessions and
  *                         rhp_gather_wide (rhp.h) as sequential walks
+ *   rhp_cpu_split_sessions  rhp_split_sessions (rhp.h) as a walk over the bytes
  *
  *   rhp_phr_parse_request the same exact parser with phr_parse_request's own
  *                         signature and outputs (pointers into buf, no length
@@ -115,6 +116,15 @@ int rhp_cpu_reply_sessions(const rhp_batch_t *batch, const rhp_session_t *sessio
 int rhp_cpu_gather_wide(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
                         const rhp_session_result_t *results, const uint64_t *req_start,
                         const rhp_req_dense_t *dreq, const rhp_http_compact_t *hc, const rhp_wide_out_t *o);
+
+/* rhp_split_sessions (rhp.h) over bytes and sess_off in host memory: every
+ * pointer of the arguments is host memory, there is no stream, `work` is not
+ * used (it must still be there, as for the device call).  A sequential walk
+ * over each session's bytes; it shares only the argument check with the
+ * kernels.  Only the bytes of [sess_off[0], sess_off[n_sessions]) are read.  The
+ * same outputs, the same overflow and tail behaviour and the same -22. */
+int rhp_cpu_split_sessions(const uint8_t *bytes, uint64_t bytes_end, const uint64_t *sess_off, uint32_t n_sessions,
+                           const rhp_split_out_t *o);
 
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */
 typedef struct rhp_phr_header {

@@ -66,12 +66,13 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 # exported C-ABI symbols of librhp.so, as declared in include/rhp.h
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
                "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
-               "rhp_gather_wide")
+               "rhp_gather_wide", "rhp_split_sessions")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
                 "rhp_cpu_classify_batch", "rhp_emu_fixup_sessions", "rhp_test_fixup_whole", "rhp_test_chunk_window",
-                "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions", "rhp_cpu_gather_wide")
+                "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions", "rhp_cpu_gather_wide",
+                "rhp_cpu_split_sessions")
 
 _rhp = None
 _host = None
@@ -143,6 +144,21 @@ assert REQ_DENSE_DTYPE.itemsize == 8 and HTTP_COMPACT_DTYPE.itemsize == 8
 def wide_work_words(n: int) -> int:
     """RHP_WIDE_WORK_WORDS (include/rhp.h)"""
     return 5 * ((n + 63) // 64) + 1
+
+
+class SplitOut(ctypes.Structure):
+    """rhp_split_out_t (include/rhp.h): the outputs of rhp_split_sessions"""
+    _fields_ = [("n_pieces", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("cap_pieces", ctypes.c_uint32),
+                ("sessions", ctypes.c_void_p), ("work", ctypes.c_void_p)]
+
+
+SPLIT_STEP_BYTES = 1024   # RHP_SPLIT_STEP_BYTES (include/rhp.h): what one wave of the mark kernel takes
+assert ctypes.sizeof(SplitOut) == 40
+
+
+def split_work_words(bytes_end: int, n_sessions: int = 0) -> int:
+    """RHP_SPLIT_WORK_WORDS (include/rhp.h)"""
+    return 25 * ((bytes_end + SPLIT_STEP_BYTES - 1) // SPLIT_STEP_BYTES) + 1
 
 
 def _torch_hip_runtime() -> str | None:
@@ -221,6 +237,8 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_gather_wide.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp, vp, vp,
                                          ctypes.POINTER(WideOut), vp]
         _rhp.rhp_gather_wide.restype = ctypes.c_int
+        _rhp.rhp_split_sessions.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint32, ctypes.POINTER(SplitOut), vp]
+        _rhp.rhp_split_sessions.restype = ctypes.c_int
     return _rhp
 
 
@@ -274,6 +292,8 @@ def host() -> ctypes.CDLL:
         _host.rhp_cpu_gather_wide.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp, vp, vp,
                                               ctypes.POINTER(WideOut)]
         _host.rhp_cpu_gather_wide.restype = ctypes.c_int
+        _host.rhp_cpu_split_sessions.argtypes = [vp, u64, vp, ctypes.c_uint32, ctypes.POINTER(SplitOut)]
+        _host.rhp_cpu_split_sessions.restype = ctypes.c_int
     return _host
 
 
@@ -1554,3 +1574,146 @@ def rebuild_records(n: int, max_headers: int, sessions, results, dreq, hc, lens1
         a[~in_use] = np.zeros((), dtype=a.dtype)
     return {"in_use": in_use, "wide": wide, "reqs": reqs, "hdrs": out_hdrs, "http": http, "req_start": req_start,
             "bodies": bodies}
+
+
+# ---------------------------------------------------------------------------
+# The split in front of the parse (rhp.h rhp_split_sessions): the sessions'
+# packed input cut at every empty line into offsets[] and rhp_session_t[] --
+# split_pieces and pack_sessions above, for input that is already in HBM.
+
+SPLIT_POISON = 0xFF   # what n_pieces, offsets, sessions and work hold before a call (tests)
+
+
+def pack_raw(session_bytes_list, first: int = 0):
+    """(buf u8, sess_off u64 [n_sessions + 1]) for session inputs packed back to back from byte `first` of the
+    buffer (the bytes before it are LF, which no session may look back at), RHP_PAD zero bytes behind them."""
+    sess_off = np.zeros(len(session_bytes_list) + 1, dtype=np.uint64)
+    sess_off[0] = first
+    if len(session_bytes_list):
+        sess_off[1:] = first + np.cumsum([len(d) for d in session_bytes_list], dtype=np.uint64)
+    end = int(sess_off[-1])
+    buf = np.zeros(end + RHP_PAD, dtype=np.uint8)
+    buf[:first] = 10
+    buf[first:end] = np.frombuffer(b"".join(session_bytes_list), dtype=np.uint8)
+    return buf, sess_off
+
+
+def _split_result(n_pieces, offsets, sessions, cap, n_sessions):
+    """(n_pieces int, offsets u64 [cap + 1], sessions SESSION_DTYPE [n_sessions]) from the bytes of the outputs"""
+    return (int(n_pieces.view(np.uint64)[0]), offsets[: 8 * (cap + 1)].view(np.uint64),
+            sessions[: 8 * n_sessions].view(SESSION_DTYPE))
+
+
+def split_sessions_cpu(buf, sess_off, cap: int | None = None, bytes_end: int | None = None):
+    """rhp_cpu_split_sessions (include/rhp_host.h): `buf` the packed bytes (u8), sess_off u64 [n_sessions + 1],
+    bytes_end (default: sess_off's last).  cap None: the exact one, from a count-only call first.  Returns
+    (n_pieces, offsets u64 [cap + 1], sessions SESSION_DTYPE [n_sessions]); every output held SPLIT_POISON
+    before the call."""
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    ns = len(sess_off) - 1
+    bytes_end = int(sess_off[-1]) if bytes_end is None else bytes_end
+    raw = np.zeros(max(bytes_end, 1) + 16, dtype=np.uint8)   # (rhp.h: bytes is 16-byte aligned)
+    at = (-raw.ctypes.data) % 16
+    b = raw[at: at + bytes_end]
+    b[:] = np.asarray(buf, dtype=np.uint8)[:bytes_end]
+    work = np.full(split_work_words(bytes_end, ns) * 8, SPLIT_POISON, dtype=np.uint8)
+
+    def call(cap):
+        n_pieces, offsets, sessions = (np.full(size, SPLIT_POISON, dtype=np.uint8) for size in
+                                       (8, 8 * (cap + 1), max(8 * ns, 1)))
+        o = SplitOut(_ptr(n_pieces), _ptr(offsets), cap, _ptr(sessions), _ptr(work))
+        rc = host().rhp_cpu_split_sessions(_ptr(b), bytes_end, _ptr(sess_off), ns, ctypes.byref(o))
+        if rc != 0:
+            raise RuntimeError(f"rhp_cpu_split_sessions failed: {rc}")
+        return _split_result(n_pieces, offsets, sessions, cap, ns)
+
+    return call(call(0)[0] if cap is None else int(cap))
+
+
+def split_sessions_device(bytes_t, bytes_end: int, sess_off_t, n_sessions: int, cap: int, guard: int = 0,
+                          fill: int = SPLIT_POISON, stream=None):
+    """One rhp_split_sessions call over device tensors (`bytes_t` u8, 16-byte aligned; sess_off_t i64 / u64
+    [n_sessions + 1]) on the stream (default: the current one).  n_pieces, offsets [cap + 1], sessions and work
+    are Guarded device buffers (guard bytes on both sides) that hold `fill` first.  Returns (outs, finish): outs
+    the Guarded buffers by name -- outs["offsets"].view and outs["sessions"].view are what rhp_parse_batch
+    (n = cap) and rhp_fixup_sessions take, on the same stream, with no host step; finish(): synchronize, check
+    the guards, (n_pieces, offsets, sessions) as split_sessions_cpu."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    cap = int(cap)
+    outs = {"n_pieces": Guarded("n_pieces", 8, guard, fill=fill),
+            "offsets": Guarded("offsets", 8 * (cap + 1), guard, fill=fill),
+            "sessions": Guarded("sessions", max(8 * n_sessions, 1), guard, fill=fill),
+            "work": Guarded("work", split_work_words(bytes_end, n_sessions) * 8, guard, fill=fill)}
+    o = SplitOut(*(outs[k].view.data_ptr() for k in ("n_pieces", "offsets")), cap,
+                 *(outs[k].view.data_ptr() for k in ("sessions", "work")))
+    vp = ctypes.c_void_p
+    rc = lib().rhp_split_sessions(vp(_addr(bytes_t)), bytes_end, vp(_addr(sess_off_t)), n_sessions, ctypes.byref(o),
+                                  vp(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_split_sessions failed: {rc}")
+
+    def finish(_keep=(bytes_t, sess_off_t)):
+        torch.cuda.synchronize()
+        if guard:
+            for x in outs.values():
+                x.check()
+        return _split_result(*(outs[k].view.cpu().numpy() for k in ("n_pieces", "offsets", "sessions")), cap, n_sessions)
+    return outs, finish
+
+
+def split_sessions_gpu(session_bytes_list, cap: int | None = None, first: int = 0, guard: int = 0):
+    """The sessions' inputs packed back to back (pack_raw) and split on the GPU.  cap None: the exact one, from
+    a count-only call first.  Returns (n_pieces, offsets, sessions) as split_sessions_cpu."""
+    import torch
+    buf, sess_off = pack_raw(session_bytes_list, first)
+    db = Guarded("bytes", buf.size, guard, data=buf)
+    dso = torch.from_numpy(sess_off.view(np.int64)).to("cuda")
+    end, ns = int(sess_off[-1]), len(session_bytes_list)
+
+    def call(cap):
+        out = split_sessions_device(db.view, end, dso, ns, cap, guard)[1]()
+        if guard:
+            db.check()
+        return out
+
+    return call(call(0)[0] if cap is None else int(cap))
+
+
+def fixup_raw_gpu(session_bytes_list, cap: int, max_headers: int = 16, impl: int = IMPL_DFA, guard: int = 0):
+    """A round from plain session input, on the GPU with no host step between the launches: rhp_split_sessions
+    -> rhp_parse_batch (n = cap, speculative, over the split's offsets) -> rhp_fixup_sessions (over the
+    split's sessions), one stream.  offsets and sessions hold zeros first, so a cap below n_pieces parses empty
+    pieces only (rhp.h); it raises once the round has run.  Returns (Result over the cap record slots, session
+    results, req_start, n_pieces, offsets u64 [cap + 1], sessions SESSION_DTYPE)."""
+    import torch
+    buf, sess_off = pack_raw(session_bytes_list)
+    end, ns, cap = int(sess_off[-1]), len(session_bytes_list), int(cap)
+    lib().rhp_set_impl(impl)
+    try:
+        db = DeviceBatch(buf, np.zeros(cap + 1, dtype=np.uint64), max_headers, MODE_HTTP, flags=BATCH_SPECULATIVE,
+                         guard=guard)
+        dso = torch.from_numpy(sess_off.view(np.int64)).to("cuda")
+        outs, finish = split_sessions_device(db.bytes, end, dso, ns, cap, guard, fill=0)
+        db.offsets = outs["offsets"].view.view(torch.int64)
+        db.launch()
+        gres = Guarded("results", ns * SESSION_RESULT_DTYPE.itemsize, guard)
+        gst = Guarded("req_start", max(cap, 1) * 8, guard)
+        d = db.desc()
+        rc = lib().rhp_fixup_sessions(ctypes.byref(d), ctypes.c_void_p(outs["sessions"].view.data_ptr()), ns,
+                                      ctypes.c_void_p(gres.view.data_ptr()), ctypes.c_void_p(gst.view.data_ptr()),
+                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
+        n_pieces, offsets, sessions = finish()
+        if n_pieces > cap:
+            raise RuntimeError(f"fixup_raw_gpu: {n_pieces} pieces do not fit cap {cap}")
+        db.host_off = offsets.copy()   # (result() describes the parsed batch over the split's offsets)
+        res = db.result()
+        if guard:
+            gres.check()
+            gst.check()
+        return (res, gres.view.cpu().numpy().view(SESSION_RESULT_DTYPE), gst.view.cpu().numpy().view(np.uint64),
+                n_pieces, offsets, sessions)
+    finally:
+        lib().rhp_set_impl(IMPL_DFA)

@@ -1,7 +1,7 @@
 /*
  * rhp_host.cpp -- the product's host entry points (rhp_host.h): the exact
  * scalar parser over a batch in host memory, the session fix-up, the dense
- * pack and the three expansions, the host classify, reply and gather, and the pointer-based
+ * pack and the three expansions, the host classify, reply, gather and split, and the pointer-based
  * rhp_phr_parse_request / rhp_http_read_cpu.  libreactor.so links them.  The
  * parser is rhp_scalar.h's (the code the kernel's rare paths run); where the
  * records sit and how they are encoded is rhp_records.h's.
@@ -17,6 +17,7 @@
 #include "rhp_classify_args.h"
 #include "rhp_reply_args.h"
 #include "rhp_gather_args.h"
+#include "rhp_split_args.h"
 #include "rhp_host_exact.h"
 
 using namespace rhp;
@@ -358,6 +359,44 @@ extern "C" int rhp_cpu_gather_wide(const rhp_batch_t *b, const rhp_session_t *se
     *o->totals = tot;
     /* (sessions that overlap, against the contract, may count a slot twice: the saturated counts fit no area) */
     if (at_slot > o->cap_slots || at_hdr > o->cap_hdrs || at_body > o->cap_body) break;   /* totals only */
+  }
+  return 0;
+}
+
+/* rhp_split_sessions (rhp.h) on the host, every pointer in host memory: a plain
+ * walk over each session's bytes with the cut rule as rhp.h words it, twice --
+ * the count first, then, when the pieces fit cap_pieces, the offsets and the
+ * sessions in the same order, and the tail.  It shares the argument check with
+ * the kernels' launcher (rhp_split_args.h) and nothing else. */
+extern "C" int rhp_cpu_split_sessions(const uint8_t *bytes, uint64_t bytes_end, const uint64_t *sess_off, uint32_t n_sessions,
+                                      const rhp_split_out_t *o)
+{
+  const int rc = rhp_split_sessions_check(bytes, bytes_end, sess_off, n_sessions, o);
+  if (rc < 0) return rc;
+  for (int pass = 0; pass < 2; pass++) {
+    uint64_t k = 0;
+    for (uint32_t s = 0; s < n_sessions; s++) {
+      const uint64_t a = sess_off[s], e = sess_off[s + 1u] < bytes_end ? sess_off[s + 1u] : bytes_end;
+      if (pass) {
+        o->sessions[s].piece_lo = (uint32_t) k;
+        o->offsets[k] = a;
+      }
+      k++;
+      for (uint64_t p = a + 2u; p < e; p++) {
+        if (bytes[p - 1u] != RHP_SPLIT_LF) continue;
+        if (bytes[p - 2u] == RHP_SPLIT_LF || (p - a >= 3u && bytes[p - 2u] == RHP_SPLIT_CR && bytes[p - 3u] == RHP_SPLIT_LF)) {
+          if (pass) o->offsets[k] = p;
+          k++;
+        }
+      }
+      if (pass) o->sessions[s].piece_hi = (uint32_t) k;
+    }
+    if (pass) {
+      for (; k <= o->cap_pieces; k++) o->offsets[k] = sess_off[n_sessions];
+      break;
+    }
+    *o->n_pieces = k;
+    if (k > o->cap_pieces) break;   /* *n_pieces only */
   }
   return 0;
 }
