@@ -705,6 +705,76 @@ int rhp_split_sessions(const uint8_t *bytes, uint64_t bytes_end,
                        const uint64_t *sess_off /* device [n_sessions + 1] */, uint32_t n_sessions,
                        const rhp_split_out_t *o, void *stream);
 
+/*
+ * The parser's other two entry points, batched: for n messages already in HBM,
+ *   int phr_parse_response(const char *buf, size_t len, int *minor_version, int *status,
+ *       const char **msg, size_t *msg_len, struct phr_header *headers, size_t *num_headers,
+ *       size_t last_len);
+ *   int phr_parse_headers(const char *buf, size_t len, struct phr_header *headers,
+ *       size_t *num_headers, size_t last_len);
+ *                       /root/reference/src/picohttpparser/picohttpparser.h:55-59
+ *                       (picohttpparser.c:411-478, 480-499)
+ * what a proxy's upstream side, a load generator or a capture analyser holds:
+ * status lines with their headers, or bare header blocks (trailers, multipart
+ * parts).  Message i is bytes[offsets[i], offsets[i+1]); as in rhp_batch_t the
+ * bytes after it (the next message, RHP_PAD zero bytes after the last) are
+ * what the reference would read past the end, and every pointer it returns is
+ * returned as an offset from the message start.
+ *   RHP_MSG_RESPONSE.  No leading CRLF is skipped.  "HTTP/1." and a digit
+ *   (fewer than 9 bytes: -2), one SP, then further SPs skipped with no end test
+ *   (the skip may run into the bytes after the message), fewer than 4 bytes
+ *   left: -2, three digits, the reason phrase up to CRLF or LF (a control byte
+ *   other than HT, or DEL: -1).  A phrase that is not empty starts with SP and
+ *   loses all its leading SPs; msg_off / msg_len are what is left (an empty
+ *   phrase: msg_off at the line end, msg_len 0).  Then the header lines.
+ *   RHP_MSG_HEADERS.  The header lines from byte 0.
+ *   Both.  last_len[i] != 0 runs is_complete first, as rhp_batch_t.last_len
+ *   says.  The header lines are those of a request: an obs-fold line gives
+ *   RHP_NAME_NULL and cannot be the first line, trailing OWS is trimmed, a
+ *   line beyond max_headers gives -1.  A header section longer than
+ *   RHP_MAX_LEN gives RHP_RET_TOOLONG and no other output (the caller parses it
+ *   with rhp_phr_parse_response / rhp_phr_parse_headers, rhp_host.h).  Records
+ *   past num_headers are unspecified.
+ * Memory.  No byte at or beyond bytes + bytes_size is read, whatever offsets
+ * holds (there the reader sees zeros); nothing is written outside msgs[0, n)
+ * and hdrs[0, n * max_headers).  A message record leaves as one 16-byte store
+ * (msgs is 16-byte aligned), a header record as one 8-byte store.
+ * -EINVAL: a NULL batch; a kind or layout other than those named; max_headers
+ * above RHP_MAX_HEADERS; n * max_headers >= 2^32; with n > 0: a NULL bytes,
+ * offsets or msgs, a NULL hdrs with max_headers > 0, bytes_size below RHP_PAD,
+ * bytes or msgs not 16-byte aligned, hdrs not 8-byte aligned (the alignments:
+ * device pointers only).  n == 0 succeeds and launches nothing.
+ * Launch contract as rhp_parse_batch: asynchronous on `stream`, no allocation,
+ * no copy, no host synchronisation; thread-safe.  One launch, one message per
+ * lane.
+ */
+enum rhp_msg_kind { RHP_MSG_RESPONSE = 0,   /* phr_parse_response, picohttpparser.c:411-478 */
+                    RHP_MSG_HEADERS  = 1 }; /* phr_parse_headers,  picohttpparser.c:480-499 */
+
+typedef struct rhp_msg {          /* 16 B; for ret <= 0 only ret is meaningful */
+  int32_t  ret;                   /* >0 bytes consumed, -1, -2, RHP_RET_TOOLONG (ret > RHP_MAX_LEN) */
+  uint16_t status;                /* RESPONSE: 100 * d0 + 10 * d1 + d2; HEADERS: 0 */
+  uint16_t msg_off, msg_len;      /* RESPONSE: reason phrase after its leading spaces; HEADERS: 0, 0 */
+  int8_t   minor_version;         /* RESPONSE; HEADERS: -1 */
+  uint8_t  reserved;              /* written 0 */
+  uint16_t num_headers;
+  uint16_t flags;                 /* written 0 */
+} rhp_msg_t;
+
+typedef struct rhp_msg_batch {
+  const uint8_t  *bytes;          /* as rhp_batch_t.bytes: 16-byte aligned, RHP_PAD zero bytes after the last message */
+  const uint64_t *offsets;        /* device [n + 1], non-decreasing */
+  uint64_t        bytes_size;
+  uint32_t        n, max_headers; /* max_headers <= RHP_MAX_HEADERS, 0 allowed */
+  uint32_t        kind;           /* enum rhp_msg_kind */
+  uint32_t        layout;         /* RHP_LAYOUT_REQUEST_MAJOR or RHP_LAYOUT_HEADER_MAJOR; any other: -EINVAL */
+  rhp_msg_t      *msgs;           /* device [n] */
+  rhp_hdr_t      *hdrs;           /* device [n * max_headers], RHP_HDR() indexing; may be NULL when max_headers == 0 */
+  const uint64_t *last_len;       /* device [n] or NULL (= all 0); contract last_len[i] <= len, as rhp_batch_t */
+} rhp_msg_batch_t;
+
+int rhp_parse_messages(const rhp_msg_batch_t *batch, void *stream);
+
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,8 @@
  *   rhp_cpu_reply_sessions, rhp_cpu_gather_wide  rhp_reply_sessions and
  *                         rhp_gather_wide (rhp.h) as sequential walks
  *   rhp_cpu_split_sessions  rhp_split_sessions (rhp.h) as a walk over the bytes
+ *   rhp_cpu_parse_messages  rhp_parse_messages (rhp.h): the kernel's templates
+ *                         over host memory
  *
  *   rhp_phr_parse_request the same exact parser with phr_parse_request's own
  *                         signature and outputs (pointers into buf, no length
@@ -126,6 +128,13 @@ int rhp_cpu_gather_wide(const rhp_batch_t *batch, const rhp_session_t *sessions,
 int rhp_cpu_split_sessions(const uint8_t *bytes, uint64_t bytes_end, const uint64_t *sess_off, uint32_t n_sessions,
                            const rhp_split_out_t *o);
 
+/* rhp_parse_messages (rhp.h) over a batch in host memory: every pointer of the
+ * batch is host memory, of any alignment, and there is no stream.  The same
+ * records and the same -22 (rhp_msg_args.h; the alignment rules are the
+ * device's alone).  As the reference, it reads the bytes after a message while
+ * the SP skip behind a response's version runs (rhp.h). */
+int rhp_cpu_parse_messages(const rhp_msg_batch_t *batch);
+
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */
 typedef struct rhp_phr_header {
   const char *name;
@@ -140,6 +149,16 @@ typedef struct rhp_phr_header {
 int rhp_phr_parse_request(const char *buf, size_t len, const char **method, size_t *method_len, const char **path,
                           size_t *path_len, int *minor_version, rhp_phr_header_t *headers, size_t *num_headers,
                           size_t last_len);
+
+/* phr_parse_response and phr_parse_headers (picohttpparser.h:55-59) with
+ * their own signatures and outputs, no length limit: what a caller runs on a
+ * message rhp_parse_messages answered with RHP_RET_TOOLONG.  *num_headers is
+ * the capacity on input and the count on output; last_len != 0 runs
+ * is_complete first.  rhp_phr_parse_response may read bytes past buf + len
+ * while they are SP (picohttpparser.c:423-425). */
+int rhp_phr_parse_response(const char *buf, size_t len, int *minor_version, int *status, const char **msg,
+                           size_t *msg_len, rhp_phr_header_t *headers, size_t *num_headers, size_t last_len);
+int rhp_phr_parse_headers(const char *buf, size_t len, rhp_phr_header_t *headers, size_t *num_headers, size_t last_len);
 
 /* http_read_request's outputs for one buffer (http.c:177-234) */
 typedef struct rhp_http_req {

@@ -66,13 +66,13 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 # exported C-ABI symbols of librhp.so, as declared in include/rhp.h
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
                "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
-               "rhp_gather_wide", "rhp_split_sessions")
+               "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
                 "rhp_cpu_classify_batch", "rhp_emu_fixup_sessions", "rhp_test_fixup_whole", "rhp_test_chunk_window",
                 "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions", "rhp_cpu_gather_wide",
-                "rhp_cpu_split_sessions")
+                "rhp_cpu_split_sessions", "rhp_cpu_parse_messages", "rhp_phr_parse_response", "rhp_phr_parse_headers")
 
 _rhp = None
 _host = None
@@ -161,6 +161,20 @@ def split_work_words(bytes_end: int, n_sessions: int = 0) -> int:
     return 25 * ((bytes_end + SPLIT_STEP_BYTES - 1) // SPLIT_STEP_BYTES) + 1
 
 
+class MsgBatch(ctypes.Structure):
+    """rhp_msg_batch_t (include/rhp.h): a batch of responses or bare header blocks for rhp_parse_messages"""
+    _fields_ = [("bytes", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("bytes_size", ctypes.c_uint64),
+                ("n", ctypes.c_uint32), ("max_headers", ctypes.c_uint32), ("kind", ctypes.c_uint32),
+                ("layout", ctypes.c_uint32), ("msgs", ctypes.c_void_p), ("hdrs", ctypes.c_void_p),
+                ("last_len", ctypes.c_void_p)]
+
+
+MSG_RESPONSE, MSG_HEADERS = 0, 1   # enum rhp_msg_kind
+MSG_DTYPE = np.dtype([("ret", "<i4"), ("status", "<u2"), ("msg_off", "<u2"), ("msg_len", "<u2"),
+                      ("minor_version", "i1"), ("reserved", "u1"), ("num_headers", "<u2"), ("flags", "<u2")])
+assert MSG_DTYPE.itemsize == 16 and ctypes.sizeof(MsgBatch) == 64
+
+
 def _torch_hip_runtime() -> str | None:
     """Path of the HIP runtime torch ships (torch/lib/libamdhip64.so), found
     without importing torch."""
@@ -239,6 +253,8 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_gather_wide.restype = ctypes.c_int
         _rhp.rhp_split_sessions.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint32, ctypes.POINTER(SplitOut), vp]
         _rhp.rhp_split_sessions.restype = ctypes.c_int
+        _rhp.rhp_parse_messages.argtypes = [ctypes.POINTER(MsgBatch), vp]
+        _rhp.rhp_parse_messages.restype = ctypes.c_int
     return _rhp
 
 
@@ -294,6 +310,13 @@ def host() -> ctypes.CDLL:
         _host.rhp_cpu_gather_wide.restype = ctypes.c_int
         _host.rhp_cpu_split_sessions.argtypes = [vp, u64, vp, ctypes.c_uint32, ctypes.POINTER(SplitOut)]
         _host.rhp_cpu_split_sessions.restype = ctypes.c_int
+        _host.rhp_cpu_parse_messages.argtypes = [ctypes.POINTER(MsgBatch)]
+        _host.rhp_cpu_parse_messages.restype = ctypes.c_int
+        _host.rhp_phr_parse_response.argtypes = [vp, sz, P(ctypes.c_int), P(ctypes.c_int), P(vp), P(sz), P(PhrHeader),
+                                                 P(sz), sz]
+        _host.rhp_phr_parse_response.restype = ctypes.c_int
+        _host.rhp_phr_parse_headers.argtypes = [vp, sz, P(PhrHeader), P(sz), sz]
+        _host.rhp_phr_parse_headers.restype = ctypes.c_int
     return _host
 
 
@@ -1717,3 +1740,90 @@ def fixup_raw_gpu(session_bytes_list, cap: int, max_headers: int = 16, impl: int
                 n_pieces, offsets, sessions)
     finally:
         lib().rhp_set_impl(IMPL_DFA)
+
+
+# The parser's other two entry points (rhp.h rhp_parse_messages): batches of
+# responses (phr_parse_response) and of bare header blocks (phr_parse_headers).
+
+MSG_POISON = 0xC3   # what msgs and hdrs hold before a call (tests): an unwritten ret reads back as -1010580541, no answer's value
+
+
+def phr_parse_message_cpu(kind: int, buf: np.ndarray, start: int, length: int, max_headers: int, last_len: int = 0):
+    """rhp_phr_parse_response / rhp_phr_parse_headers (the host drop-ins) on bytes buf[start:start+length].
+    Returns (ret, minor, status, msg(off,len), [(name_off|-1, name_len, value_off, value_len)]) with offsets from
+    `start`; a header block: minor -1, status 0, msg (0, 0)."""
+    h = host()
+    hdrs = (PhrHeader * max(max_headers, 1))()
+    msg, ml, nh = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_size_t(max_headers)
+    minor, status = ctypes.c_int(-1), ctypes.c_int(0)
+    base = buf.ctypes.data + start
+    if kind == MSG_RESPONSE:
+        ret = h.rhp_phr_parse_response(base, length, ctypes.byref(minor), ctypes.byref(status), ctypes.byref(msg),
+                                       ctypes.byref(ml), hdrs, ctypes.byref(nh), last_len)
+    else:
+        ret = h.rhp_phr_parse_headers(base, length, hdrs, ctypes.byref(nh), last_len)
+    if ret <= 0:
+        return ret, -1, 0, (0, 0), []
+    rel = lambda p: (p or 0) - base
+    hs = [(rel(x.name) if x.name else -1, x.name_len, rel(x.value), x.value_len) for x in hdrs[: nh.value]]
+    return ret, minor.value, status.value, ((rel(msg.value), ml.value) if kind == MSG_RESPONSE else (0, 0)), hs
+
+
+def _msg_result(msgs, hdrs, n, max_headers, layout):
+    """(msgs MSG_DTYPE [n], hdrs HDR_DTYPE [n, max_headers]) from the bytes of the two record arrays"""
+    return (msgs[: 16 * n].view(MSG_DTYPE),
+            hdr_view(hdrs[: 8 * n * max_headers].view(HDR_DTYPE), n, max_headers, layout))
+
+
+def parse_messages_cpu(buf, off, kind: int, max_headers: int = 16, layout: int = LAYOUT_REQUEST_MAJOR, last_len=None):
+    """rhp_cpu_parse_messages (include/rhp_host.h): `buf` the packed messages with RHP_PAD zero bytes behind
+    them (u8), off u64 [n + 1], last_len u64 [n] or None.  Returns (msgs MSG_DTYPE [n], hdrs HDR_DTYPE
+    [n, max_headers]); both held MSG_POISON before the call."""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1
+    ll = None if last_len is None else np.ascontiguousarray(last_len, dtype=np.uint64)
+    msgs = np.full(max(16 * n, 1), MSG_POISON, dtype=np.uint8)
+    hdrs = np.full(max(8 * n * max_headers, 1), MSG_POISON, dtype=np.uint8)
+    b = MsgBatch(_ptr(buf), _ptr(off), buf.size, n, max_headers, kind, layout, _ptr(msgs), _ptr(hdrs),
+                 _ptr(ll) if ll is not None else None)
+    rc = host().rhp_cpu_parse_messages(ctypes.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"rhp_cpu_parse_messages failed: {rc}")
+    return _msg_result(msgs, hdrs, n, max_headers, layout)
+
+
+def parse_messages_device(bytes_t, bytes_size: int, off_t, n: int, kind: int, max_headers: int, layout: int,
+                          msgs_t, hdrs_t, last_len_t=None, stream=None):
+    """One rhp_parse_messages call over device tensors on the stream (default: the current one): bytes_t u8
+    (16-byte aligned), off_t i64 / u64 [n + 1], last_len_t the same [n] or None; the records are left in msgs_t
+    (u8, 16 * n bytes) and hdrs_t (u8, 8 * n * max_headers bytes; None when max_headers == 0).  Nothing is
+    synchronised or copied: the tensors are the call's only inputs and outputs."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    b = MsgBatch(_addr(bytes_t), _addr(off_t), bytes_size, n, max_headers, kind, layout, _addr(msgs_t), _addr(hdrs_t),
+                 _addr(last_len_t))
+    rc = lib().rhp_parse_messages(ctypes.byref(b), ctypes.c_void_p(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_parse_messages failed: {rc}")
+
+
+def parse_messages_gpu(buf, off, kind: int, max_headers: int = 16, layout: int = LAYOUT_REQUEST_MAJOR, last_len=None,
+                       guard: int = 0, fill: int = MSG_POISON):
+    """The messages parsed on the GPU.  bytes, msgs and hdrs are Guarded device buffers (guard bytes on both
+    sides, checked after the call); msgs and hdrs hold `fill` first.  Returns (msgs, hdrs) as parse_messages_cpu."""
+    import torch
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1
+    db = Guarded("bytes", buf.size, guard, data=buf if buf.flags.writeable else buf.copy())   # (torch takes writable arrays)
+    gm = Guarded("msgs", max(16 * n, 1), guard, fill=fill)
+    gh = Guarded("hdrs", max(8 * n * max_headers, 1), guard, fill=fill)
+    doff = torch.from_numpy(off.view(np.int64).copy()).to("cuda")
+    dll = None if last_len is None else torch.from_numpy(np.array(last_len, dtype=np.uint64).view(np.int64)).to("cuda")
+    parse_messages_device(db.view, buf.size, doff, n, kind, max_headers, layout, gm.view, gh.view, dll)
+    torch.cuda.synchronize()
+    if guard:
+        for g in (db, gm, gh):
+            g.check()
+    return _msg_result(gm.view.cpu().numpy(), gh.view.cpu().numpy(), n, max_headers, layout)

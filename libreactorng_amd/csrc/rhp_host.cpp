@@ -1,8 +1,9 @@
 /*
  * rhp_host.cpp -- the product's host entry points (rhp_host.h): the exact
  * scalar parser over a batch in host memory, the session fix-up, the dense
- * pack and the three expansions, the host classify, reply, gather and split, and the pointer-based
- * rhp_phr_parse_request / rhp_http_read_cpu.  libreactor.so links them.  The
+ * pack and the three expansions, the host classify, reply, gather and split, the
+ * message parse (responses, header blocks), and the pointer-based
+ * rhp_phr_parse_request / _response / _headers and rhp_http_read_cpu.  libreactor.so links them.  The
  * parser is rhp_scalar.h's (the code the kernel's rare paths run); where the
  * records sit and how they are encoded is rhp_records.h's.
  */
@@ -18,6 +19,7 @@
 #include "rhp_reply_args.h"
 #include "rhp_gather_args.h"
 #include "rhp_split_args.h"
+#include "rhp_msg_args.h"
 #include "rhp_host_exact.h"
 
 using namespace rhp;
@@ -401,6 +403,27 @@ extern "C" int rhp_cpu_split_sessions(const uint8_t *bytes, uint64_t bytes_end, 
   return 0;
 }
 
+/* rhp_parse_messages (rhp.h) on the host, every pointer in host memory: the
+ * kernel's templates (rhp_scalar.h) over PlainBytes, message by message.  It
+ * shares the argument check with the launcher (rhp_msg_args.h).  As the
+ * reference, it may read the bytes after a message (rhp.h). */
+extern "C" int rhp_cpu_parse_messages(const rhp_msg_batch_t *b)
+{
+  const int rc = rhp_msg_batch_check(b, 0);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const bool hmajor = b->layout == RHP_LAYOUT_HEADER_MAJOR;
+  const uint64_t hs_req = hmajor ? 1u : b->max_headers, hs_hdr = hmajor ? b->n : 1u;
+  for (uint32_t i = 0; i < b->n; i++) {
+    const uint64_t off = b->offsets[i], len = b->offsets[i + 1] - off;
+    const uint64_t ll = b->last_len ? b->last_len[i] : 0;
+    PlainBytes B{b->bytes + off};
+    OutMsg<PlainMsgStore> out{{b->msgs + i, b->hdrs ? b->hdrs + i * hs_req : nullptr, hs_hdr}};
+    if (b->kind == RHP_MSG_RESPONSE) scalar_message_t<RHP_MSG_RESPONSE>(B, len, ll, b->max_headers, out);
+    else scalar_message_t<RHP_MSG_HEADERS>(B, len, ll, b->max_headers, out);
+  }
+  return 0;
+}
+
 /* ---- the pointer-based host parser: phr_parse_request's own outputs ---- */
 
 namespace {
@@ -467,6 +490,62 @@ extern "C" int rhp_phr_parse_request(const char *buf, size_t len, const char **m
   }
   PlainBytes B{b};
   return scalar_phr_t(B, len, (uint32_t) (max < 0xffffffffu ? max : 0xffffffffu), o);
+}
+
+namespace {
+
+/* rhp_scalar.h output policy writing phr_parse_response's / phr_parse_headers'
+ * outputs (picohttpparser.c:461-465, 486); a NULL status: the header block's */
+struct OutPhrMsg {
+  const uint8_t *base;
+  int *minor_version, *status;
+  const char **msg;
+  size_t *msg_len;
+  rhp_phr_header_t *h;
+  size_t *num_headers;
+  void begin()
+  {
+    if (status) { *minor_version = -1; *status = 0; *msg = nullptr; *msg_len = 0; }
+    *num_headers = 0;
+  }
+  int fail(int code) { return code; }
+  void header(uint32_t n, bool fold, uint64_t name, uint64_t name_len, uint64_t vs, uint64_t vlen)
+  {
+    h[n].name = fold ? nullptr : (const char *) base + name;
+    h[n].name_len = (size_t) name_len;
+    h[n].value = (const char *) base + vs;
+    h[n].value_len = (size_t) vlen;
+  }
+  int done(uint64_t p, int minor, uint32_t st, uint64_t m, uint64_t m_len, uint32_t n)
+  {
+    if (status) { *minor_version = minor; *status = (int) st; *msg = (const char *) base + m; *msg_len = (size_t) m_len; }
+    *num_headers = n;
+    return (int) p;
+  }
+};
+
+template <uint32_t KIND>
+int phr_message(OutPhrMsg &o, const char *buf, size_t len, size_t last_len)
+{
+  const size_t max = *o.num_headers;
+  PlainBytes B{(const uint8_t *) buf};
+  return scalar_message_t<KIND>(B, len, last_len, (uint32_t) (max < 0xffffffffu ? max : 0xffffffffu), o);
+}
+
+}  // namespace
+
+extern "C" int rhp_phr_parse_response(const char *buf, size_t len, int *minor_version, int *status, const char **msg,
+                                      size_t *msg_len, rhp_phr_header_t *headers, size_t *num_headers, size_t last_len)
+{
+  OutPhrMsg o{(const uint8_t *) buf, minor_version, status, msg, msg_len, headers, num_headers};
+  return phr_message<RHP_MSG_RESPONSE>(o, buf, len, last_len);
+}
+
+extern "C" int rhp_phr_parse_headers(const char *buf, size_t len, rhp_phr_header_t *headers, size_t *num_headers,
+                                     size_t last_len)
+{
+  OutPhrMsg o{(const uint8_t *) buf, nullptr, nullptr, nullptr, nullptr, headers, num_headers};
+  return phr_message<RHP_MSG_HEADERS>(o, buf, len, last_len);
 }
 
 extern "C" int rhp_http_read_cpu(uint8_t *buf, size_t len, rhp_http_req_t *req, rhp_phr_header_t *fields,

@@ -1,5 +1,6 @@
 /*
- * rhp_scalar.h -- exact scalar request parser, compiled for host and device.
+ * rhp_scalar.h -- exact scalar request parser, compiled for host and device
+ * (and, for rhp_parse_messages, the response and header-block parsers).
  *
  * The DFA kernel (rhp_kernel.hip) hands a request to this path when its fast
  * table cannot decide it alone: the buffer ends before the request completes
@@ -10,6 +11,7 @@
  *
  * Semantics followed (all /root/reference/...):
  *   phr_parse_request  src/picohttpparser/picohttpparser.c:71-94,134-195,245-409
+ *   phr_parse_response, phr_parse_headers  picohttpparser.c:411-499
  *   http_read_request  src/reactor/http.c:73-160,167-234; memcasecmp data.c:11-28
  */
 #ifndef RHP_SCALAR_H
@@ -174,6 +176,170 @@ RHP_HD int scalar_phr_t(Bytes &B, uint64_t len, uint32_t max, Out &out)
   return out.done(p, tok, minor, n);
 }
 
+/* ---- the other two entry points of the parser: a response and a bare header
+ * block (rhp.h rhp_parse_messages).  Their Out gives begin(), fail(code),
+ * header(...) as above and done(p, minor, status, msg, msg_len, n). ---- */
+
+#define RHP_FAIL(code) do { return out.fail(code); } while (0)
+#define RHP_EOF() do { if (p == len) RHP_FAIL(kPartial); } while (0)
+#define RHP_CRLF() do { ++p; RHP_EOF(); if (B(p++) != '\n') RHP_FAIL(kBad); } while (0)
+
+/* The header lines from byte p up to and behind the empty line that ends them
+ * (parse_headers, picohttpparser.c:263-339), for the response and the bare
+ * header block.  It is scalar_phr_t's loop stated a second time: sharing one
+ * statement moves the request kernels' code (DESIGN.md 3.9 has the numbers), so
+ * tests/test_messages.py holds the two to each other on the fuzz set.  Header k
+ * goes to out.header(k), n counts them (0 on entry).  Returns 0 with p behind
+ * the empty line, or what out.fail() made of -1 / -2. */
+template <class Bytes, class Out>
+RHP_HD int scalar_header_lines_t(Bytes &B, uint64_t len, uint32_t max, Out &out, uint64_t &p, uint32_t &n)
+{
+  for (;;) {
+    RHP_EOF();
+    if (B(p) == '\r') { RHP_CRLF(); break; }
+    if (B(p) == '\n') { ++p; break; }
+    if (n == max) RHP_FAIL(kBad);
+    uint64_t name = p, name_len = 0;
+    bool fold = n != 0 && is_ows(B(p));
+    if (!fold) {
+      for (;;) {
+        uint32_t c = B(p);
+        if (c == ':') break;
+        if (!is_tchar(c)) RHP_FAIL(kBad);
+        ++p;
+        RHP_EOF();
+      }
+      name_len = p - name;
+      if (name_len == 0) RHP_FAIL(kBad);
+      ++p;
+      for (;; ++p) {
+        RHP_EOF();
+        if (!is_ows(B(p))) break;
+      }
+    }
+    uint64_t vs = p;
+    uint32_t c;
+    for (;; ++p) {
+      RHP_EOF();
+      c = B(p);
+      if ((c < 0x20u && c != '\t') || c == 0x7fu) break;
+    }
+    uint64_t ve = p;
+    if (c == '\r') RHP_CRLF();
+    else if (c == '\n') ++p;
+    else RHP_FAIL(kBad);
+    while (ve > vs && is_ows(B(ve - 1))) --ve;
+    out.header(n, fold, name, name_len, vs, ve - vs);
+    ++n;
+  }
+  return 0;
+}
+
+/* Where a message's answer goes as batch records (rhp_msg_t, rhp_hdr_t).  Store
+ * says how a whole record leaves: st.msg(v), st.hdr(k, v) -- plain assignments
+ * on the host, one 16-byte and one 8-byte store on the device. */
+template <class Store>
+struct OutMsg {
+  Store st;
+  RHP_HDM void begin() {}
+  RHP_HDM int put(int32_t ret, uint32_t status, uint64_t msg, uint64_t msg_len, int minor, uint32_t n)
+  {
+    rhp_msg_t v;
+    v.ret = ret;
+    v.status = (uint16_t) status;
+    v.msg_off = (uint16_t) msg;
+    v.msg_len = (uint16_t) msg_len;
+    v.minor_version = (int8_t) minor;
+    v.reserved = 0;
+    v.num_headers = (uint16_t) n;
+    v.flags = 0;
+    st.msg(v);
+    return ret;
+  }
+  RHP_HDM int fail(int code) { return put(code, 0, 0, 0, -1, 0); }
+  RHP_HDM void header(uint32_t n, bool fold, uint64_t name, uint64_t name_len, uint64_t vs, uint64_t vlen)
+  {
+    rhp_hdr_t o;
+    o.name_off = fold ? (uint16_t) RHP_NAME_NULL : (uint16_t) name;
+    o.name_len = (uint16_t) name_len;
+    o.value_off = (uint16_t) vs;
+    o.value_len = (uint16_t) vlen;
+    st.hdr(n, o);
+  }
+  RHP_HDM int done(uint64_t p, int minor, uint32_t status, uint64_t msg, uint64_t msg_len, uint32_t n)
+  {
+    if (p > RHP_MAX_LEN) return fail(RHP_RET_TOOLONG);   /* u16 records cannot hold it */
+    return put((int32_t) p, status, msg, msg_len, minor, n);
+  }
+};
+
+/* the host's Store: record k at h[k * hs] (RHP_HDR()'s two layouts) */
+struct PlainMsgStore {
+  rhp_msg_t *m;
+  rhp_hdr_t *h;
+  uint64_t hs;
+  RHP_HDM void msg(const rhp_msg_t &v) const { *m = v; }
+  RHP_HDM void hdr(uint32_t k, const rhp_hdr_t &v) const { h[k * hs] = v; }
+};
+
+/* Parse one response (parse_response, picohttpparser.c:411-452): no leading
+ * empty line is skipped; b may be read beyond len by the SP skip behind the
+ * version (batch contract). */
+template <class Bytes, class Out>
+RHP_HD int scalar_response_t(Bytes &B, uint64_t len, uint32_t max, Out &out)
+{
+  uint64_t p = 0;
+  out.begin();
+  if (len < 9) RHP_FAIL(kPartial);
+  if (B(0) != 'H' || B(1) != 'T' || B(2) != 'T' || B(3) != 'P' || B(4) != '/' || B(5) != '1' || B(6) != '.' ||
+      B(7) - '0' > 9u)
+    RHP_FAIL(kBad);
+  const int minor = (int) B(7) - '0';
+  p = 8;
+  if (B(p) != ' ') RHP_FAIL(kBad);
+  do ++p; while (B(p) == ' ');     /* no EOF test: may run past len */
+  if ((int64_t) len - (int64_t) p < 4) RHP_FAIL(kPartial);
+  uint32_t status = 0;
+  for (int k = 0; k < 3; k++) {
+    const uint32_t d = B(p++) - '0';
+    if (d > 9u) RHP_FAIL(kBad);
+    status = 10u * status + d;
+  }
+  /* the reason phrase with the spaces before it, to the line's end (get_token_to_eol, :134-195) */
+  uint64_t ms = p;
+  uint32_t c;
+  for (;; ++p) {
+    RHP_EOF();
+    c = B(p);
+    if ((c < 0x20u && c != '\t') || c == 0x7fu) break;
+  }
+  const uint64_t me = p;
+  if (c == '\r') RHP_CRLF();
+  else if (c == '\n') ++p;
+  else RHP_FAIL(kBad);
+  if (me != ms) {
+    if (B(ms) != ' ') RHP_FAIL(kBad);   /* garbage behind the status code */
+    do ++ms; while (B(ms) == ' ');      /* ends at the line end at the latest */
+  }
+  uint32_t n = 0;
+  if (const int e = scalar_header_lines_t(B, len, max, out, p, n)) return e;
+  return out.done(p, minor, status, ms, me - ms, n);
+}
+
+/* Parse one bare header block (phr_parse_headers, picohttpparser.c:480-499) */
+template <class Bytes, class Out>
+RHP_HD int scalar_headers_t(Bytes &B, uint64_t len, uint32_t max, Out &out)
+{
+  uint64_t p = 0;
+  uint32_t n = 0;
+  out.begin();
+  if (const int e = scalar_header_lines_t(B, len, max, out, p, n)) return e;
+  return out.done(p, -1, 0, 0, 0, n);
+}
+#undef RHP_CRLF
+#undef RHP_EOF
+#undef RHP_FAIL
+
 template <class Bytes>
 RHP_HD int scalar_phr_t(Bytes &B, uint64_t len, uint32_t max, rhp_req_t *r, rhp_hdr_t *h, uint64_t hs)
 {
@@ -218,6 +384,20 @@ RHP_HD int is_complete(const uint8_t *b, uint64_t len, uint64_t last_len)
 {
   PlainBytes B{b};
   return is_complete_t(B, len, last_len);
+}
+
+/* One message of rhp_parse_messages: is_complete first when last_len != 0
+ * (picohttpparser.c:469-471, 490-492), then the parse its kind names. */
+template <uint32_t KIND, class Bytes, class Out>
+RHP_HD int scalar_message_t(Bytes &B, uint64_t len, uint64_t last_len, uint32_t max, Out &out)
+{
+  const int pre = last_len ? is_complete_t(B, len, last_len) : 0;
+  if (pre != 0) {
+    out.begin();
+    return out.fail(pre);
+  }
+  if constexpr (KIND == RHP_MSG_RESPONSE) return scalar_response_t(B, len, max, out);
+  else return scalar_headers_t(B, len, max, out);
 }
 
 /* ---- http_read_request framing (http.c:177-234) over a parsed request ---- */
