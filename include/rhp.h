@@ -775,6 +775,94 @@ typedef struct rhp_msg_batch {
 
 int rhp_parse_messages(const rhp_msg_batch_t *batch, void *stream);
 
+/*
+ * The parser's fourth entry point, batched: for n streams whose newly arrived
+ * bytes lie in HBM,
+ *   ssize_t phr_decode_chunked(struct phr_chunked_decoder *decoder, char *buf, size_t *bufsz);
+ *                       /root/reference/src/picohttpparser/picohttpparser.h:62-81
+ *                       (picohttpparser.c:523-636)
+ * the resumable de-framer of a chunked body: a caller who parsed a response's
+ * headers (rhp_parse_messages) feeds it whatever arrived of the body, call
+ * after call.  Stream i's piece is bytes[offsets[i], offsets[i+1]) (`buf`, its
+ * length `*bufsz` on entry) and decoders[i] its struct phr_chunked_decoder,
+ * zero-filled (but for consume_trailer) before the stream's first call and
+ * carried from call to call as it is left.  The call leaves what the
+ * reference leaves, value for value: results[i].ret, results[i].size (*bufsz
+ * on return, written on every exit), the decoder's three fields on every exit,
+ * and every byte of the piece: the decoded bytes in [0, size); right behind
+ * them the bytes the reference's closing memmove (:632-633) carries down (the
+ * `ret` bytes that follow the body's end; on -1 the bytes from the offending
+ * one on); every byte beyond those keeps its value.
+ *   The state machine.  A piece is walked from the decoder's state on; when
+ *   the piece ends inside a state the answer is -2 and the state is kept.
+ *   RHP_CHUNKED_IN_CHUNK_SIZE   hex digits (0-9, A-F, a-f; leading zeros count)
+ *                       shift into bytes_left_in_chunk, hex_count counts them
+ *                       across calls: 16 at most, a 17th gives -1; the first
+ *                       other byte ends them (hex_count back to 0) and is -1
+ *                       when no digit came before it.
+ *   RHP_CHUNKED_IN_CHUNK_EXT    the rest of the size line is skipped up to its
+ *                       LF with no look at its bytes (a bare LF ends a size
+ *                       line).  Then bytes_left_in_chunk != 0: the data; == 0
+ *                       (the last chunk): with consume_trailer the trailer
+ *                       lines, without it the body ends at this LF.
+ *   RHP_CHUNKED_IN_CHUNK_DATA   min(bytes_left_in_chunk, what the piece holds)
+ *                       bytes move down behind the decoded ones and are
+ *                       counted off; the data is not looked at.
+ *   RHP_CHUNKED_IN_CHUNK_CRLF   any run of CRs, then the LF: the next size line;
+ *                       any other byte gives -1.
+ *   RHP_CHUNKED_IN_TRAILERS_LINE_HEAD   any run of CRs; then an LF ends the body
+ *                       (the empty line; an empty trailer section is just it);
+ *                       any other byte starts a line,
+ *   RHP_CHUNKED_IN_TRAILERS_LINE_MIDDLE   which is skipped up to its LF.
+ *   The body's end leaves the state as it is then (IN_CHUNK_EXT or
+ *   IN_TRAILERS_LINE_HEAD).  An empty piece gives -2 and changes nothing.
+ * Corrupt decoder.  state > 5 (the reference asserts) or hex_count > 16 (the
+ * reference cannot leave it): ret = -1, size = 0, the piece and the decoder
+ * untouched.
+ * Memory.  A piece's start and end are clamped to bytes_size (and the end to
+ * at least the start) whatever offsets holds.  Only a piece's own bytes are
+ * looked at: no pad is asked for.  They are loaded as bytes or as the aligned
+ * dwords that hold them (inside the aligned 16-byte lines that hold the piece;
+ * so with bytes_size a multiple of 4 no byte at or beyond bytes + bytes_size
+ * is read).  Stores go to the piece's own bytes only -- a byte of a
+ * neighbouring piece, which belongs to another wave, is not even rewritten
+ * with its own value.  decoders[i] and results[i] are each read and written
+ * as one 16-byte access.
+ * -EINVAL (rhp_chunked_args.h): a NULL batch; reserved != 0; with n > 0 a NULL
+ * bytes, offsets, decoders or results; bytes, decoders or results not 16-byte
+ * aligned (device pointers only).  n == 0 succeeds and launches nothing.
+ * Launch contract as rhp_parse_messages: asynchronous on `stream`, one launch,
+ * no allocation, no copy, no host synchronisation; thread-safe.  One wave per
+ * stream.
+ */
+enum { RHP_CHUNKED_IN_CHUNK_SIZE, RHP_CHUNKED_IN_CHUNK_EXT, RHP_CHUNKED_IN_CHUNK_DATA,
+       RHP_CHUNKED_IN_CHUNK_CRLF, RHP_CHUNKED_IN_TRAILERS_LINE_HEAD,
+       RHP_CHUNKED_IN_TRAILERS_LINE_MIDDLE };     /* picohttpparser.c:501-508, same values */
+
+typedef struct rhp_chunked {            /* 16 B: struct phr_chunked_decoder; zero-filled before a stream's first call */
+  uint64_t bytes_left_in_chunk;
+  uint8_t  consume_trailer;             /* the caller's; never written */
+  uint8_t  hex_count;                   /* _hex_count */
+  uint8_t  state;                       /* _state, RHP_CHUNKED_IN_* */
+  uint8_t  reserved[5];                 /* kept as they are */
+} rhp_chunked_t;
+
+typedef struct rhp_chunked_result {     /* 16 B */
+  int64_t  ret;    /* >= 0: end of the body found, `ret` undecoded bytes follow the decoded ones; -1 error; -2 incomplete */
+  uint64_t size;   /* *bufsz on return: decoded bytes at the piece's start */
+} rhp_chunked_result_t;
+
+typedef struct rhp_chunked_batch {
+  uint8_t              *bytes;       /* device, 16-byte aligned, read and written */
+  const uint64_t       *offsets;     /* device [n + 1]: stream i's new input is bytes[offsets[i], offsets[i+1]) */
+  uint64_t              bytes_size;
+  uint32_t              n, reserved; /* reserved must be 0 */
+  rhp_chunked_t        *decoders;    /* device [n], 16-byte aligned, read and written */
+  rhp_chunked_result_t *results;     /* device [n], 16-byte aligned */
+} rhp_chunked_batch_t;
+
+int rhp_decode_chunked(const rhp_chunked_batch_t *batch, void *stream);
+
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,9 @@
  *   rhp_cpu_split_sessions  rhp_split_sessions (rhp.h) as a walk over the bytes
  *   rhp_cpu_parse_messages  rhp_parse_messages (rhp.h): the kernel's templates
  *                         over host memory
+ *   rhp_cpu_decode_chunked  rhp_decode_chunked (rhp.h): the scalar statement of
+ *                         phr_decode_chunked over host memory, and
+ *                         rhp_phr_decode_chunked, the pointer-based drop-in
  *
  *   rhp_phr_parse_request the same exact parser with phr_parse_request's own
  *                         signature and outputs (pointers into buf, no length
@@ -43,6 +46,7 @@
 #define RHP_HOST_H
 
 #include <stdint.h>
+#include <sys/types.h>
 #include "rhp.h"
 
 #ifdef __cplusplus
@@ -159,6 +163,19 @@ int rhp_phr_parse_request(const char *buf, size_t len, const char **method, size
 int rhp_phr_parse_response(const char *buf, size_t len, int *minor_version, int *status, const char **msg,
                            size_t *msg_len, rhp_phr_header_t *headers, size_t *num_headers, size_t last_len);
 int rhp_phr_parse_headers(const char *buf, size_t len, rhp_phr_header_t *headers, size_t *num_headers, size_t last_len);
+
+/* rhp_decode_chunked (rhp.h) over a batch in host memory: every pointer of the
+ * batch is host memory, of any alignment, and there is no stream.  The same
+ * results, decoders and bytes and the same -22 (rhp_chunked_args.h; the
+ * alignment rules are the device's alone).  Only a piece's own bytes are read. */
+int rhp_cpu_decode_chunked(const rhp_chunked_batch_t *batch);
+
+/* phr_decode_chunked and phr_decode_chunked_is_in_data (picohttpparser.h:62-86)
+ * with their own signatures: rhp_chunked_t has struct phr_chunked_decoder's
+ * layout.  A corrupt decoder (rhp.h) gives -1 and *bufsz = 0 where the
+ * reference asserts. */
+ssize_t rhp_phr_decode_chunked(rhp_chunked_t *decoder, char *buf, size_t *bufsz);
+int rhp_phr_decode_chunked_is_in_data(rhp_chunked_t *decoder);
 
 /* http_read_request's outputs for one buffer (http.c:177-234) */
 typedef struct rhp_http_req {

@@ -66,13 +66,14 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 # exported C-ABI symbols of librhp.so, as declared in include/rhp.h
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
                "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
-               "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages")
+               "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages", "rhp_decode_chunked")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
                 "rhp_cpu_classify_batch", "rhp_emu_fixup_sessions", "rhp_test_fixup_whole", "rhp_test_chunk_window",
                 "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions", "rhp_cpu_gather_wide",
-                "rhp_cpu_split_sessions", "rhp_cpu_parse_messages", "rhp_phr_parse_response", "rhp_phr_parse_headers")
+                "rhp_cpu_split_sessions", "rhp_cpu_parse_messages", "rhp_phr_parse_response", "rhp_phr_parse_headers",
+                "rhp_cpu_decode_chunked", "rhp_phr_decode_chunked", "rhp_phr_decode_chunked_is_in_data")
 
 _rhp = None
 _host = None
@@ -175,6 +176,22 @@ MSG_DTYPE = np.dtype([("ret", "<i4"), ("status", "<u2"), ("msg_off", "<u2"), ("m
 assert MSG_DTYPE.itemsize == 16 and ctypes.sizeof(MsgBatch) == 64
 
 
+class ChunkedBatch(ctypes.Structure):
+    """rhp_chunked_batch_t (include/rhp.h): the new bytes of n chunked streams for rhp_decode_chunked"""
+    _fields_ = [("bytes", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("bytes_size", ctypes.c_uint64),
+                ("n", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("decoders", ctypes.c_void_p),
+                ("results", ctypes.c_void_p)]
+
+
+# enum RHP_CHUNKED_IN_* (rhp.h; picohttpparser.c:501-508)
+(CHUNKED_IN_CHUNK_SIZE, CHUNKED_IN_CHUNK_EXT, CHUNKED_IN_CHUNK_DATA, CHUNKED_IN_CHUNK_CRLF, CHUNKED_IN_TRAILERS_LINE_HEAD,
+ CHUNKED_IN_TRAILERS_LINE_MIDDLE) = range(6)
+CHUNKED_DTYPE = np.dtype([("bytes_left_in_chunk", "<u8"), ("consume_trailer", "u1"), ("hex_count", "u1"), ("state", "u1"),
+                          ("reserved", "u1", (5,))])   # rhp_chunked_t = struct phr_chunked_decoder
+CHUNKED_RESULT_DTYPE = np.dtype([("ret", "<i8"), ("size", "<u8")])
+assert CHUNKED_DTYPE.itemsize == 16 and CHUNKED_RESULT_DTYPE.itemsize == 16 and ctypes.sizeof(ChunkedBatch) == 48
+
+
 def _torch_hip_runtime() -> str | None:
     """Path of the HIP runtime torch ships (torch/lib/libamdhip64.so), found
     without importing torch."""
@@ -255,6 +272,8 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_split_sessions.restype = ctypes.c_int
         _rhp.rhp_parse_messages.argtypes = [ctypes.POINTER(MsgBatch), vp]
         _rhp.rhp_parse_messages.restype = ctypes.c_int
+        _rhp.rhp_decode_chunked.argtypes = [ctypes.POINTER(ChunkedBatch), vp]
+        _rhp.rhp_decode_chunked.restype = ctypes.c_int
     return _rhp
 
 
@@ -317,6 +336,12 @@ def host() -> ctypes.CDLL:
         _host.rhp_phr_parse_response.restype = ctypes.c_int
         _host.rhp_phr_parse_headers.argtypes = [vp, sz, P(PhrHeader), P(sz), sz]
         _host.rhp_phr_parse_headers.restype = ctypes.c_int
+        _host.rhp_cpu_decode_chunked.argtypes = [ctypes.POINTER(ChunkedBatch)]
+        _host.rhp_cpu_decode_chunked.restype = ctypes.c_int
+        _host.rhp_phr_decode_chunked.argtypes = [vp, vp, P(sz)]
+        _host.rhp_phr_decode_chunked.restype = ctypes.c_ssize_t
+        _host.rhp_phr_decode_chunked_is_in_data.argtypes = [vp]
+        _host.rhp_phr_decode_chunked_is_in_data.restype = ctypes.c_int
     return _host
 
 
@@ -1827,3 +1852,68 @@ def parse_messages_gpu(buf, off, kind: int, max_headers: int = 16, layout: int =
         for g in (db, gm, gh):
             g.check()
     return _msg_result(gm.view.cpu().numpy(), gh.view.cpu().numpy(), n, max_headers, layout)
+
+
+# The parser's fourth entry point (rhp.h rhp_decode_chunked): the resumable de-framer of chunked bodies over
+# the new bytes of a batch of streams.
+
+CHUNKED_POISON = 0xC3   # what results hold before a call (tests): an unwritten ret is no answer's value
+
+
+def phr_decode_chunked_cpu(decoder: np.ndarray, piece: np.ndarray):
+    """rhp_phr_decode_chunked (the host drop-in for phr_decode_chunked) on one piece (u8, decoded in place) with
+    one decoder (CHUNKED_DTYPE [1], carried on in place).  Returns (ret, size)."""
+    sz = ctypes.c_size_t(piece.size)
+    ret = host().rhp_phr_decode_chunked(_ptr(decoder), _ptr(piece), ctypes.byref(sz))
+    return int(ret), int(sz.value)
+
+
+def decode_chunked_cpu(buf, off, decoders):
+    """rhp_cpu_decode_chunked (include/rhp_host.h): `buf` the packed pieces (u8), off u64 [n + 1], decoders
+    CHUNKED_DTYPE [n].  Nothing passed in is changed.  Returns (results CHUNKED_RESULT_DTYPE [n], decoders
+    CHUNKED_DTYPE [n], bytes u8 as the call left them); results held CHUNKED_POISON before the call."""
+    buf = np.array(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    dec = np.array(decoders, dtype=CHUNKED_DTYPE)
+    n = len(off) - 1
+    res = np.full(max(16 * n, 1), CHUNKED_POISON, dtype=np.uint8)
+    b = ChunkedBatch(_ptr(buf), _ptr(off), buf.size, n, 0, _ptr(dec), _ptr(res))
+    rc = host().rhp_cpu_decode_chunked(ctypes.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"rhp_cpu_decode_chunked failed: {rc}")
+    return res[: 16 * n].view(CHUNKED_RESULT_DTYPE), dec, buf
+
+
+def decode_chunked_device(bytes_t, bytes_size: int, off_t, n: int, decoders_t, results_t, stream=None):
+    """One rhp_decode_chunked call over device tensors on the stream (default: the current one): bytes_t u8
+    (16-byte aligned, decoded in place), off_t i64 / u64 [n + 1], decoders_t and results_t u8, 16 * n bytes each
+    (16-byte aligned; the decoders are carried on in place).  Nothing is synchronised or copied: the tensors are
+    the call's only inputs and outputs."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    b = ChunkedBatch(_addr(bytes_t), _addr(off_t), bytes_size, n, 0, _addr(decoders_t), _addr(results_t))
+    rc = lib().rhp_decode_chunked(ctypes.byref(b), ctypes.c_void_p(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_decode_chunked failed: {rc}")
+
+
+def decode_chunked_gpu(buf, off, decoders, guard: int = 0, fill: int = CHUNKED_POISON, bytes_size: int | None = None):
+    """The pieces decoded on the GPU.  bytes, decoders and results are Guarded device buffers (guard bytes on
+    both sides, checked after the call); results hold `fill` first.  bytes_size: what the batch states (default:
+    all of buf).  Returns (results, decoders, bytes) as decode_chunked_cpu."""
+    import torch
+    buf = np.array(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    dec = np.array(decoders, dtype=CHUNKED_DTYPE)
+    n = len(off) - 1
+    db = Guarded("bytes", max(buf.size, 1), guard, data=buf)
+    gd = Guarded("decoders", max(16 * n, 1), guard, data=dec.view(np.uint8).reshape(-1))
+    gr = Guarded("results", max(16 * n, 1), guard, fill=fill)
+    doff = torch.from_numpy(off.view(np.int64).copy()).to("cuda")
+    decode_chunked_device(db.view, buf.size if bytes_size is None else bytes_size, doff, n, gd.view, gr.view)
+    torch.cuda.synchronize()
+    if guard:
+        for g in (db, gd, gr):
+            g.check()
+    return (gr.view.cpu().numpy()[: 16 * n].view(CHUNKED_RESULT_DTYPE), gd.view.cpu().numpy()[: 16 * n].view(CHUNKED_DTYPE),
+            db.view.cpu().numpy()[: buf.size])

@@ -1,6 +1,6 @@
 /*
  * rhp_device.h -- the device helpers that more than one of rhp_writer.hip,
- * rhp_classify.hip, rhp_reply.hip and rhp_gather.hip use, stated once: the
+ * rhp_classify.hip, rhp_reply.hip, rhp_gather.hip and rhp_chunked.hip use, stated once: the
  * inclusive scan of a wave, the wave's copy of a byte range, the flush of a
  * wave's LDS stage, and the search and the test that give a record slot its
  * session.  Device code only; every function is inlined into its caller.
@@ -35,7 +35,19 @@ __device__ __forceinline__ T wave_incl_scan(T v, uint32_t lane)
  * instruction) from funnel-shifted aligned source dwords, then the tail bytes;
  * below 128 bytes a byte per lane.  The read contract: no byte outside the
  * aligned dwords that hold [src, src + len) is read -- the dword past the
- * last one a 16-byte step needs is loaded only if the range reaches it */
+ * last one a 16-byte step needs is loaded only if the range reaches it.
+ * Overlap: safe for d <= src (a move down in place, rhp_chunked.hip), by the
+ * order of its steps -- the head bytes, then the body 1 KiB at a time, then the
+ * tail bytes (below 128 bytes: 64 bytes at a time); step t covers bytes
+ * [a_t, b_t) of the range, ascending and back to back.  With g = src - d, the
+ * stores of step t land on src + [a_t - g, b_t - g), and the source bytes step
+ * u uses are src + [a_u, b_u) (a dword's bytes outside that range are loaded
+ * and shifted out by alignbyte), so a store of step t can reach a source byte
+ * of step u only for u <= t.  Those are loaded already: d and src may alias as
+ * far as the compiler knows, so it keeps a lane's loads and stores in program
+ * order; the wave issues every instruction for all its lanes at once; and a
+ * step's store waits (vmcnt) for that step's loads, which return for the whole
+ * wave.  DESIGN.md 3.10 */
 __device__ __forceinline__ void put(uint8_t *d, const uint8_t *src, uint64_t len, uint32_t lane)
 {
   if (len < 128) {

@@ -2,8 +2,8 @@
  * rhp_host.cpp -- the product's host entry points (rhp_host.h): the exact
  * scalar parser over a batch in host memory, the session fix-up, the dense
  * pack and the three expansions, the host classify, reply, gather and split, the
- * message parse (responses, header blocks), and the pointer-based
- * rhp_phr_parse_request / _response / _headers and rhp_http_read_cpu.  libreactor.so links them.  The
+ * message parse (responses, header blocks), the chunked decoder, and the pointer-based
+ * rhp_phr_parse_request / _response / _headers, rhp_phr_decode_chunked and rhp_http_read_cpu.  libreactor.so links them.  The
  * parser is rhp_scalar.h's (the code the kernel's rare paths run); where the
  * records sit and how they are encoded is rhp_records.h's.
  */
@@ -20,6 +20,7 @@
 #include "rhp_gather_args.h"
 #include "rhp_split_args.h"
 #include "rhp_msg_args.h"
+#include "rhp_chunked_args.h"
 #include "rhp_host_exact.h"
 
 using namespace rhp;
@@ -422,6 +423,60 @@ extern "C" int rhp_cpu_parse_messages(const rhp_msg_batch_t *b)
     else scalar_message_t<RHP_MSG_HEADERS>(B, len, ll, b->max_headers, out);
   }
   return 0;
+}
+
+/* rhp_decode_chunked (rhp.h) on the host, every pointer in host memory: the
+ * scalar statement (rhp_scalar.h decode_chunked_t) over PlainBytes and the
+ * byte-wise forward move, stream by stream, with the launcher's argument check
+ * (rhp_chunked_args.h) and the kernel's clamp of a piece's ends. */
+namespace {
+
+int64_t decode_chunked_piece(rhp_chunked_t *d, uint8_t *buf, uint64_t len, uint64_t *size)
+{
+  if (RHP_CHUNKED_CORRUPT(d->state, d->hex_count)) {
+    *size = 0;
+    return kBad;
+  }
+  PlainBytes B{buf};
+  PlainMove M{buf};
+  uint64_t left = d->bytes_left_in_chunk;
+  uint32_t hex = d->hex_count, st = d->state;
+  const int64_t ret = decode_chunked_t(B, M, len, d->consume_trailer != 0, left, hex, st, size);
+  d->bytes_left_in_chunk = left;
+  d->hex_count = (uint8_t) hex;
+  d->state = (uint8_t) st;
+  return ret;
+}
+
+}  // namespace
+
+extern "C" int rhp_cpu_decode_chunked(const rhp_chunked_batch_t *b)
+{
+  const int rc = rhp_chunked_batch_check(b, 0);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  for (uint32_t i = 0; i < b->n; i++) {
+    uint64_t off = b->offsets[i], end = b->offsets[i + 1];
+    off = off < b->bytes_size ? off : b->bytes_size;
+    end = end < off ? off : end < b->bytes_size ? end : b->bytes_size;
+    uint64_t size = 0;
+    const int64_t ret = decode_chunked_piece(&b->decoders[i], b->bytes + off, end - off, &size);
+    b->results[i].ret = ret;
+    b->results[i].size = size;
+  }
+  return 0;
+}
+
+extern "C" ssize_t rhp_phr_decode_chunked(rhp_chunked_t *decoder, char *buf, size_t *bufsz)
+{
+  uint64_t size = 0;
+  const int64_t ret = decode_chunked_piece(decoder, (uint8_t *) buf, *bufsz, &size);
+  *bufsz = (size_t) size;
+  return (ssize_t) ret;
+}
+
+extern "C" int rhp_phr_decode_chunked_is_in_data(rhp_chunked_t *decoder)
+{
+  return decoder->state == RHP_CHUNKED_IN_CHUNK_DATA;   /* picohttpparser.c:638-641 */
 }
 
 /* ---- the pointer-based host parser: phr_parse_request's own outputs ---- */

@@ -894,6 +894,83 @@ RHP_HD uint32_t fixup_step_stop(uint32_t from, uint32_t p_hi, uint64_t other)
   return p_hi - from < kFixupStep ? p_hi : from + kFixupStep;
 }
 
+/* phr_decode_chunked (picohttpparser.c:523-636; rhp.h rhp_decode_chunked spells
+ * the states out) over one piece of `len` bytes: B(p) reads byte p of the
+ * piece, move(dst, src, n) carries n of its bytes down (dst < src, the ranges
+ * may overlap).  left, hex and st are the decoder's bytes_left_in_chunk,
+ * hex_count and state, read and left as the reference leaves them on every
+ * exit; *size is *bufsz on return.  Returns the reference's value.  One state
+ * per turn of the loop, each scanning from src; a piece that ends inside a
+ * state leaves the loop with -2.  The caller has refused a corrupt decoder
+ * (rhp_chunked_args.h).  rhp_chunked.hip walks the same states a window of 64
+ * bytes at a time. */
+template <class Bytes, class Move>
+RHP_HD int64_t decode_chunked_t(Bytes &B, Move &move, uint64_t len, bool consume_trailer, uint64_t &left, uint32_t &hex,
+                                uint32_t &st, uint64_t *size)
+{
+  uint64_t src = 0, dst = 0;
+  int64_t ret = kPartial;
+  for (;;) {
+    if (st == RHP_CHUNKED_IN_CHUNK_DATA) {   /* needs no byte: it runs on an ended piece too */
+      const uint64_t avail = len - src, n = avail < left ? avail : left;
+      if (dst != src && n) move(dst, src, n);
+      src += n;
+      dst += n;
+      left -= n;
+      if (left) break;
+      st = RHP_CHUNKED_IN_CHUNK_CRLF;
+    }
+    if (src == len) break;
+    if (st == RHP_CHUNKED_IN_CHUNK_SIZE) {
+      int v = hexval(B(src));
+      for (; v >= 0 && hex < 16u; v = hexval(B(src))) {
+        left = (left << 4) | (uint64_t) v;
+        hex++;
+        if (++src == len) break;
+      }
+      if (src == len) break;
+      if (v >= 0 || hex == 0) {   /* a 17th digit; no digit at all */
+        ret = kBad;
+        break;
+      }
+      hex = 0;
+      st = RHP_CHUNKED_IN_CHUNK_EXT;
+    } else if (st == RHP_CHUNKED_IN_CHUNK_EXT || st == RHP_CHUNKED_IN_TRAILERS_LINE_MIDDLE) {
+      while (src < len && B(src) != '\n') src++;
+      if (src == len) break;
+      src++;
+      if (st == RHP_CHUNKED_IN_TRAILERS_LINE_MIDDLE || (left == 0 && consume_trailer)) st = RHP_CHUNKED_IN_TRAILERS_LINE_HEAD;
+      else if (left != 0) st = RHP_CHUNKED_IN_CHUNK_DATA;
+      else {
+        ret = (int64_t) (len - src);
+        break;
+      }
+    } else {   /* IN_CHUNK_CRLF, IN_TRAILERS_LINE_HEAD: a run of CRs, then the byte that decides */
+      while (src < len && B(src) == '\r') src++;
+      if (src == len) break;
+      const bool lf = B(src) == '\n';
+      if (st == RHP_CHUNKED_IN_CHUNK_CRLF) {
+        if (!lf) {
+          ret = kBad;
+          break;
+        }
+        src++;
+        st = RHP_CHUNKED_IN_CHUNK_SIZE;
+      } else {
+        src++;
+        if (lf) {
+          ret = (int64_t) (len - src);
+          break;
+        }
+        st = RHP_CHUNKED_IN_TRAILERS_LINE_MIDDLE;
+      }
+    }
+  }
+  if (dst != src && src < len) move(dst, src, len - src);
+  *size = dst;
+  return ret;
+}
+
 }  // namespace rhp
 
 #endif
