@@ -11,6 +11,11 @@ decoder and every byte of the piece:
   GPU  the kernel on every set as one launch, results poisoned first and guard bytes on both sides of bytes,
        decoders and results; the multi-call streams chained on the device; all single-call records in one launch
        behind a non-zero offsets[0]; offsets that run past bytes_size
+tests/test_decode_chunked_sweep.py holds twins, live reference and kernel to two sweeps whose expected values follow
+from how their pieces are built (tests/decode_chunked_sweep.py), not from the golden file: the overlapping move at
+every (gap, destination offset mod 16, length) around the 128-byte threshold and the 1 KiB step edges, gaps 1, 8 and
+13..17 among them, and every scanning state entered at every lane of the 64-byte window, its token ending in that
+window, at its end and in the ones behind it -- complete, cut into two calls, and wrong.
 """
 from __future__ import annotations
 
@@ -24,6 +29,7 @@ import pytest
 
 import libreactorng_amd as rhp
 import decode_chunked_sets as ds
+import decode_chunked_sweep as sw
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "decode_chunked.npz")
@@ -316,10 +322,12 @@ def wave_move(mem, d, s, n, log):
 def test_wave_move_model_equals_memmove():
     """the overlap argument of DESIGN.md 3.10 run as a model: for every gap 1..40, every destination offset mod 16
     and lengths 0..200, 1000..1100 and 2040..2060 the wave's move leaves what memmove leaves, no store leaves
-    [dst, dst + len) and no load leaves the aligned dwords that hold the source"""
-    lengths = list(range(0, 201)) + list(range(1000, 1101)) + list(range(2040, 2061))
+    [dst, dst + len) and no load leaves the aligned dwords that hold the source.  The lengths of the move sweep
+    (tests/decode_chunked_sweep.py, up to 2084) are run here too; test_gpu_move_sweep runs that sweep's gaps, offsets
+    and lengths through the compiled put on the device."""
+    lengths = sorted(set(range(0, 201)) | set(range(1000, 1101)) | set(range(2040, 2061)) | set(sw.MOVE_LENGTHS))
     rng = np.random.default_rng(5)
-    orig = rng.integers(0, 256, 64 + 16 + 40 + 2060 + 64, dtype=np.uint8)
+    orig = rng.integers(0, 256, 64 + 16 + 40 + max(lengths) + 64, dtype=np.uint8)
     for gap in range(1, 41):
         for o in range(16):
             d = 64 + o
