@@ -863,6 +863,91 @@ typedef struct rhp_chunked_batch {
 
 int rhp_decode_chunked(const rhp_chunked_batch_t *batch, void *stream);
 
+/*
+ * Between the two calls above: how the body of every message
+ * rhp_parse_messages parsed is framed, with the header lookup of
+ * rhp_classify_batch over the same records, in one launch.  The framing is the
+ * reference's rule for a request that is not a GET,
+ *   http_read_request   src/reactor/http.c:204-233
+ * applied to the message's header records:
+ *   encoding = http_field_lookup(fields, count, "Transfer-Encoding");
+ *   length   = http_field_lookup(fields, count, "Content-Length");
+ * `batch` is the batch as rhp_parse_messages left it on `stream`, either kind
+ * and either layout; last_len is not looked at.  For message i:
+ *   Not ready.  msgs[i].ret <= 0 gives result = -1 for ret == -1,
+ *   RHP_RET_TOOLONG for RHP_RET_TOOLONG and 0 for anything else (http.c:194-195),
+ *   body_kind RHP_FRAME_NONE, body_len 0 and every field absent; of such a
+ *   message nothing but msgs[i].ret is read.  A message whose bytes do not lie
+ *   inside the batch's -- offsets[i] + ret above bytes_size rounded down to a
+ *   multiple of 4; a batch that keeps its RHP_PAD has none -- counts as not
+ *   ready too: result 0.
+ *   Lookup.  te and cl are the values of the first record k <
+ *   min(num_headers, max_headers) whose name is not NULL (an obs-fold line) and
+ *   is string_equal_case to Transfer-Encoding and to Content-Length (as
+ *   rhp_classify_batch compares: equal lengths, a..z mapped to A..Z, no other
+ *   byte).  Only the first match counts: a first match with an empty value
+ *   makes the header absent, even when a later duplicate has a value.
+ *   cl not empty and te not empty: result -1.
+ *   cl not empty alone: RHP_FRAME_LENGTH, body_len = strtoull(cl, NULL, 10) as
+ *   glibc's C locale gives it: a sign is accepted and '-' negates mod 2^64, no
+ *   digit gives 0, overflow saturates to 2^64 - 1.  result is 1 whether or not
+ *   the body has arrived: the caller's completeness test is the reference's own,
+ *   len < ret + body_len in size_t arithmetic, i.e. mod 2^64 (http.c:213).
+ *   Otherwise te not empty: it must be `chunked` (7 bytes, a..z mapped to A..Z:
+ *   data_equal_case, http.c:223), else result -1; then RHP_FRAME_CHUNKED.
+ *   Otherwise RHP_FRAME_NONE.  What that means for a response -- a status that
+ *   has no body, or a body that runs until the connection closes -- is the
+ *   caller's decision from msgs[i].status: the reference has no rule for it
+ *   and this call invents none.
+ *   Decoders.  With decoders != NULL, decoders[i] of an RHP_FRAME_CHUNKED
+ *   message is written with one 16-byte store: all zero but consume_trailer,
+ *   what rhp_decode_chunked wants to find when the body starts.  Every other
+ *   message's decoder is not touched, not even rewritten with its own value.
+ *   Fields.  fields[j * n + i] is what rhp_classify_batch documents for name j,
+ *   offsets from the message's start; {RHP_NAME_NULL, 0} for a missing header
+ *   and for a message that is not ready.
+ * Memory.  No byte at or beyond bytes + bytes_size is read, whatever offsets or
+ * the records hold: every offset that becomes an address is checked against
+ * the message's own ret first, and a record whose name -- for the two framing
+ * names also its value -- does not lie inside [0, ret) matches nothing (no
+ * parsed record is like that).  Records of a message that is not ready and
+ * records k >= num_headers are never read.  Name and value bytes are read as
+ * the aligned dwords that hold them, and only those of records whose name_len
+ * is a name's.  Nothing is written outside frames[0, n), fields[0, n_names * n)
+ * and the armed decoders; a frame leaves as one 16-byte store.
+ * -EINVAL (rhp_frame_args.h): a NULL batch or f; whatever rhp_parse_messages
+ * refuses about the batch (last_len apart); n_names above
+ * RHP_CLASSIFY_MAX_NAMES; an empty name or one longer than
+ * RHP_CLASSIFY_NAME_MAX; n_names > 0 with a NULL text, names or fields; with
+ * n > 0 a NULL frames, frames or decoders not 16-byte aligned (device pointers
+ * only); consume_trailer > 1; reserved != 0.  n == 0 succeeds and launches
+ * nothing.
+ * Launch contract as rhp_classify_batch: one launch, asynchronous on `stream`,
+ * no allocation, no copy, no synchronisation; the names travel in the kernel
+ * argument and the caller's tables are free when the call returns;
+ * thread-safe.  One message per lane.
+ */
+enum { RHP_FRAME_NONE = 0, RHP_FRAME_LENGTH = 1, RHP_FRAME_CHUNKED = 2 };
+
+typedef struct rhp_frame {        /* 16 B, leaves as one 16-byte store */
+  int32_t  result;                /* 1 framing decided; 0 the message is not there yet; -1 malformed; RHP_RET_TOOLONG */
+  uint32_t body_kind;             /* RHP_FRAME_* ; NONE unless result == 1 */
+  uint64_t body_len;              /* LENGTH: strtoull of the value, as u64; otherwise 0 */
+} rhp_frame_t;
+
+typedef struct rhp_frame_args {
+  const uint8_t    *text;         /* host: the bytes of the lookup names (as rhp_classify_t) */
+  const rhp_span_t *names;        /* host [n_names] */
+  uint32_t          n_names;      /* 0 .. RHP_CLASSIFY_MAX_NAMES; 0: framing only */
+  uint32_t          consume_trailer; /* 0 or 1: what an armed decoder gets */
+  rhp_fieldref_t   *fields;       /* device [n_names * n], name-major, as rhp_classify_t.fields */
+  rhp_frame_t      *frames;       /* device [n], 16-byte aligned */
+  rhp_chunked_t    *decoders;     /* device [n], 16-byte aligned, or NULL */
+  uint64_t          reserved;     /* must be 0 */
+} rhp_frame_args_t;
+
+int rhp_frame_messages(const rhp_msg_batch_t *batch, const rhp_frame_args_t *f, void *stream);
+
 
 #ifdef __cplusplus
 }

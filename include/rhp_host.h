@@ -139,6 +139,14 @@ int rhp_cpu_split_sessions(const uint8_t *bytes, uint64_t bytes_end, const uint6
  * the SP skip behind a response's version runs (rhp.h). */
 int rhp_cpu_parse_messages(const rhp_msg_batch_t *batch);
 
+/* rhp_frame_messages (rhp.h) over a batch in host memory, as
+ * rhp_cpu_parse_messages left it: every pointer of the batch and of `f` is host
+ * memory, of any alignment, and there is no stream.  The same frames, fields
+ * and armed decoders and the same -22 (rhp_frame_args.h; the alignment rules
+ * are the device's alone).  Of a message's bytes only names and values inside
+ * [0, ret) are read. */
+int rhp_cpu_frame_messages(const rhp_msg_batch_t *batch, const rhp_frame_args_t *f);
+
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */
 typedef struct rhp_phr_header {
   const char *name;

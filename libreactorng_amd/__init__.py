@@ -66,14 +66,15 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 # exported C-ABI symbols of librhp.so, as declared in include/rhp.h
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
                "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
-               "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages", "rhp_decode_chunked")
+               "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages", "rhp_decode_chunked", "rhp_frame_messages")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
                 "rhp_cpu_classify_batch", "rhp_emu_fixup_sessions", "rhp_test_fixup_whole", "rhp_test_chunk_window",
                 "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions", "rhp_cpu_gather_wide",
                 "rhp_cpu_split_sessions", "rhp_cpu_parse_messages", "rhp_phr_parse_response", "rhp_phr_parse_headers",
-                "rhp_cpu_decode_chunked", "rhp_phr_decode_chunked", "rhp_phr_decode_chunked_is_in_data")
+                "rhp_cpu_decode_chunked", "rhp_phr_decode_chunked", "rhp_phr_decode_chunked_is_in_data",
+                "rhp_cpu_frame_messages")
 
 _rhp = None
 _host = None
@@ -192,6 +193,18 @@ CHUNKED_RESULT_DTYPE = np.dtype([("ret", "<i8"), ("size", "<u8")])
 assert CHUNKED_DTYPE.itemsize == 16 and CHUNKED_RESULT_DTYPE.itemsize == 16 and ctypes.sizeof(ChunkedBatch) == 48
 
 
+class FrameArgs(ctypes.Structure):
+    """rhp_frame_args_t (include/rhp.h): the lookup names and the outputs of rhp_frame_messages"""
+    _fields_ = [("text", ctypes.c_void_p), ("names", ctypes.c_void_p), ("n_names", ctypes.c_uint32),
+                ("consume_trailer", ctypes.c_uint32), ("fields", ctypes.c_void_p), ("frames", ctypes.c_void_p),
+                ("decoders", ctypes.c_void_p), ("reserved", ctypes.c_uint64)]
+
+
+FRAME_NONE, FRAME_LENGTH, FRAME_CHUNKED = 0, 1, 2   # enum RHP_FRAME_*
+FRAME_DTYPE = np.dtype([("result", "<i4"), ("body_kind", "<u4"), ("body_len", "<u8")])   # rhp_frame_t
+assert FRAME_DTYPE.itemsize == 16 and ctypes.sizeof(FrameArgs) == 56
+
+
 def _torch_hip_runtime() -> str | None:
     """Path of the HIP runtime torch ships (torch/lib/libamdhip64.so), found
     without importing torch."""
@@ -274,6 +287,8 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_parse_messages.restype = ctypes.c_int
         _rhp.rhp_decode_chunked.argtypes = [ctypes.POINTER(ChunkedBatch), vp]
         _rhp.rhp_decode_chunked.restype = ctypes.c_int
+        _rhp.rhp_frame_messages.argtypes = [ctypes.POINTER(MsgBatch), ctypes.POINTER(FrameArgs), vp]
+        _rhp.rhp_frame_messages.restype = ctypes.c_int
     return _rhp
 
 
@@ -342,6 +357,8 @@ def host() -> ctypes.CDLL:
         _host.rhp_phr_decode_chunked.restype = ctypes.c_ssize_t
         _host.rhp_phr_decode_chunked_is_in_data.argtypes = [vp]
         _host.rhp_phr_decode_chunked_is_in_data.restype = ctypes.c_int
+        _host.rhp_cpu_frame_messages.argtypes = [ctypes.POINTER(MsgBatch), ctypes.POINTER(FrameArgs)]
+        _host.rhp_cpu_frame_messages.restype = ctypes.c_int
     return _host
 
 
@@ -1917,3 +1934,97 @@ def decode_chunked_gpu(buf, off, decoders, guard: int = 0, fill: int = CHUNKED_P
             g.check()
     return (gr.view.cpu().numpy()[: 16 * n].view(CHUNKED_RESULT_DTYPE), gd.view.cpu().numpy()[: 16 * n].view(CHUNKED_DTYPE),
             db.view.cpu().numpy()[: buf.size])
+
+
+# Between the two (rhp.h rhp_frame_messages): the body framing of every message rhp_parse_messages parsed
+# (http.c:204-233 over its header records), the header lookup of rhp_classify_batch over the same records, and
+# the decoders rhp_decode_chunked starts from.
+
+FRAME_POISON = 0xC3   # what frames, fields and decoders hold before a call (tests): no answer's value
+
+
+def _frame_result(frames, fields, decoders, n, n_names):
+    """(frames FRAME_DTYPE [n], fields FIELDREF_DTYPE [n_names, n], decoders CHUNKED_DTYPE [n] | None) from the
+    bytes of the three outputs"""
+    return (frames[: 16 * n].view(FRAME_DTYPE), fields[: 4 * n_names * n].view(FIELDREF_DTYPE).reshape(n_names, n),
+            None if decoders is None else decoders[: 16 * n].view(CHUNKED_DTYPE))
+
+
+def frame_messages_cpu(buf, off, kind: int, msgs, hdrs, names=(), max_headers: int = 16,
+                       layout: int = LAYOUT_REQUEST_MAJOR, consume_trailer: int = 0, decoders: bool = True,
+                       bytes_size: int | None = None):
+    """rhp_cpu_frame_messages (include/rhp_host.h) over the records parse_messages_cpu returned: msgs MSG_DTYPE
+    [n], hdrs HDR_DTYPE [n, max_headers] (put back into `layout`).  bytes_size: what the batch states (default:
+    all of buf).  Returns (frames FRAME_DTYPE [n], fields FIELDREF_DTYPE [n_names, n], decoders CHUNKED_DTYPE [n]
+    or None); all three held FRAME_POISON before the call."""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1
+    m = np.ascontiguousarray(msgs).view(np.uint8).reshape(-1)
+    h = np.ascontiguousarray(hdrs.T if layout == LAYOUT_HEADER_MAJOR else hdrs).view(np.uint8).reshape(-1)
+    text, nm, _ = classify_tables(names)
+    frames = np.full(max(16 * n, 1), FRAME_POISON, dtype=np.uint8)
+    fields = np.full(max(4 * len(nm) * n, 1), FRAME_POISON, dtype=np.uint8)
+    dec = np.full(max(16 * n, 1), FRAME_POISON, dtype=np.uint8) if decoders else None
+    b = MsgBatch(_ptr(buf), _ptr(off), buf.size if bytes_size is None else bytes_size, n, max_headers, kind, layout,
+                 _ptr(m) if m.size else None, _ptr(h) if h.size else None, None)
+    f = FrameArgs(_ptr(text), _ptr(nm) if len(nm) else None, len(nm), consume_trailer, _ptr(fields) if len(nm) else None,
+                  _ptr(frames), _ptr(dec) if decoders else None, 0)
+    rc = host().rhp_cpu_frame_messages(ctypes.byref(b), ctypes.byref(f))
+    if rc != 0:
+        raise RuntimeError(f"rhp_cpu_frame_messages failed: {rc}")
+    return _frame_result(frames, fields, dec, n, len(nm))
+
+
+def frame_messages_device(bytes_t, bytes_size: int, off_t, n: int, kind: int, max_headers: int, layout: int, msgs_t,
+                          hdrs_t, frames_t, names=(), fields_t=None, decoders_t=None, consume_trailer: int = 0,
+                          stream=None):
+    """One rhp_frame_messages call over device tensors on the stream (default: the current one): the batch as
+    parse_messages_device left it; frames_t u8 (16 * n bytes, 16-byte aligned), fields_t u8 (4 * len(names) * n
+    bytes), decoders_t u8 (16 * n bytes, 16-byte aligned) or None.  Nothing is synchronised or copied: the tensors
+    are the call's only inputs and outputs (the names travel in the launch)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    text, nm, _ = classify_tables(names)
+    b = MsgBatch(_addr(bytes_t), _addr(off_t), bytes_size, n, max_headers, kind, layout, _addr(msgs_t), _addr(hdrs_t), None)
+    f = FrameArgs(_ptr(text), _ptr(nm) if len(nm) else None, len(nm), consume_trailer, _addr(fields_t) if len(nm) else None,
+                  _addr(frames_t), _addr(decoders_t), 0)
+    rc = lib().rhp_frame_messages(ctypes.byref(b), ctypes.byref(f), ctypes.c_void_p(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_frame_messages failed: {rc}")
+
+
+def frame_messages_gpu(buf, off, kind: int, names=(), max_headers: int = 16, layout: int = LAYOUT_REQUEST_MAJOR,
+                       consume_trailer: int = 0, decoders: bool = True, guard: int = 0, fill: int = FRAME_POISON,
+                       records=None, bytes_size: int | None = None):
+    """The messages parsed (rhp_parse_messages) and framed (rhp_frame_messages) on the GPU, on one stream.
+    bytes, frames, fields and decoders are Guarded device buffers (guard bytes on both sides, checked after the
+    call); the three outputs hold `fill` first.  records: (msgs, hdrs) as parse_messages_cpu returns them, copied
+    in instead of parsing (tests: crafted records).  Returns (frames, fields, decoders) as frame_messages_cpu."""
+    import torch
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n, nn = len(off) - 1, len(names)
+    db = Guarded("bytes", buf.size, guard, data=buf if buf.flags.writeable else buf.copy())
+    gm = Guarded("msgs", max(16 * n, 1), 0, fill=MSG_POISON)
+    gh = Guarded("hdrs", max(8 * n * max_headers, 1), 0, fill=MSG_POISON)
+    gf = Guarded("frames", max(16 * n, 1), guard, fill=fill)
+    gl = Guarded("fields", max(4 * nn * n, 1), guard, fill=fill)
+    gd = Guarded("decoders", max(16 * n, 1), guard, fill=fill) if decoders else None
+    doff = torch.from_numpy(off.view(np.int64).copy()).to("cuda")
+    size = buf.size if bytes_size is None else bytes_size
+    if records is None:
+        parse_messages_device(db.view, size, doff, n, kind, max_headers, layout, gm.view, gh.view)
+    else:
+        m, h = records
+        h = np.ascontiguousarray(h.T if layout == LAYOUT_HEADER_MAJOR else h)
+        for g, a in ((gm, np.ascontiguousarray(m)), (gh, h)):
+            if a.size:
+                g.view[: a.nbytes].copy_(torch.from_numpy(a.view(np.uint8).reshape(-1).copy()))
+    frame_messages_device(db.view, size, doff, n, kind, max_headers, layout, gm.view, gh.view, gf.view, names, gl.view,
+                          gd.view if decoders else None, consume_trailer)
+    torch.cuda.synchronize()
+    if guard:
+        for g in (db, gf, gl) + ((gd,) if decoders else ()):
+            g.check()
+    return _frame_result(gf.view.cpu().numpy(), gl.view.cpu().numpy(), gd.view.cpu().numpy() if decoders else None, n, nn)

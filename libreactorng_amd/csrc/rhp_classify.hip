@@ -27,6 +27,11 @@
  * load, compare, absent fill and route match again: the forms of stating them
  * once that were tried, and why none is here, are in DESIGN 3.5.  The launchers
  * share fill_params.
+ *
+ * rhp_frame_messages (rhp.h) is the lookup over the rhp_msg_t / rhp_hdr_t
+ * records rhp_parse_messages leaves, with the framing of http.c:204-233 decided
+ * in the same walk: its kernel stands here because it shares fold4, same_text,
+ * CTables and pack_tables.
  */
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -36,6 +41,8 @@
 #include "rhp.h"
 #include "rhp_classify_args.h"
 #include "rhp_device.h"
+#include "rhp_frame_args.h"
+#include "rhp_scalar.h"
 
 namespace {
 
@@ -444,6 +451,148 @@ void fill_params(P &p, const rhp_batch_t *b, const rhp_classify_t *c, const uint
   p.n_routes = c->n_routes;
 }
 
+/* ---- rhp_frame_messages ---- */
+
+/* the framing names and `chunked`, folded, lie in the tables' route text (a
+ * frame call has no routes), each at a dword; they take the mask bits above the
+ * caller's names */
+constexpr uint32_t kTeBit = 1u << RHP_CLASSIFY_MAX_NAMES, kClBit = kTeBit << 1;
+constexpr uint32_t kTeLen = 17u, kClLen = 14u, kChunkedLen = 7u;
+constexpr uint32_t kTextAt = offsetof(CTables, text) / 4u;                   /* dword index into the tables */
+constexpr uint32_t kTeAt = kTextAt, kClAt = kTextAt + 8u, kChunkedAt = kTextAt + 16u;
+static_assert(kTeLen <= 32u && kClLen <= 32u && kChunkedLen <= 32u && kTextDwords >= 24u, "eight dwords each");
+static_assert(offsetof(CTables, name) == 0 && kTeLen <= RHP_CLASSIFY_NAME_MAX && kClLen <= RHP_CLASSIFY_NAME_MAX, "");
+
+struct FParams {
+  CTables         t;          /* first, as CParams */
+  const uint8_t  *bytes;
+  const uint64_t *offsets;
+  uint64_t        readable;   /* rhp_frame_readable */
+  const uint4    *msgs;
+  const uint2    *hdrs;
+  uint32_t       *fields;
+  uint4          *frames, *decoders;
+  uint32_t        n, m, n_names, consume_trailer;
+  uint32_t        s_req, s_hdr;   /* record k of message i: hdrs[i * s_req + k * s_hdr] */
+};
+static_assert(offsetof(FParams, t) == 0, "the tables lead the argument");
+static_assert(sizeof(FParams) <= 4096, "a kernel argument holds 4 KiB");
+static_assert(sizeof(rhp_msg_t) == 16 && sizeof(rhp_frame_t) == 16 && sizeof(rhp_chunked_t) == 16 &&
+              offsetof(rhp_msg_t, num_headers) == 12 && offsetof(rhp_frame_t, body_len) == 8 &&
+              offsetof(rhp_chunked_t, consume_trailer) == 8, "records as 16-byte accesses");
+
+/* strtoull10 (rhp_scalar.h) over the len >= 1 bytes at src, read as the aligned
+ * dwords that hold them: those of the first 24 bytes up front (independent
+ * loads), then, only while digits go on, a dependent byte at a time.  The same
+ * num_step over the same bytes, zeros behind the value's end. */
+__device__ __forceinline__ uint64_t value_number(const uint8_t *src, uint32_t len)
+{
+  constexpr uint32_t kWin = 24u;   /* strtoull10's kNumWindow */
+  const uintptr_t a = (uintptr_t) src;
+  const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t) 3);
+  const uint32_t sh = (uint32_t) a & 3u, nd = (sh + len + 3u) >> 2;
+  uint32_t d[kWin / 4u + 1u];
+#pragma unroll
+  for (uint32_t q = 0; q <= kWin / 4u; q++) d[q] = q < nd ? w[q] : 0u;
+  uint32_t st = 0;
+  bool neg = false, ovf = false;
+  uint64_t v = 0;
+#pragma unroll
+  for (uint32_t q = 0; q < kWin / 4u; q++) {
+    const uint32_t x = __builtin_amdgcn_alignbyte(d[q + 1u], d[q], sh);
+#pragma unroll
+    for (uint32_t e = 0; e < 4u; e++) rhp::num_step(4u * q + e < len ? (x >> (8u * e)) & 0xffu : 0u, st, neg, ovf, v);
+  }
+  for (uint32_t j = kWin; st != 2u && j < len; j++) {
+    const uint32_t at = sh + j;
+    rhp::num_step((w[at >> 2] >> (8u * (at & 3u))) & 0xffu, st, neg, ovf, v);
+  }
+  return ovf ? ~0ull : neg ? 0 - v : v;
+}
+
+/* One message per lane, rhp_classify_kernel's mapping: the lane loads its
+ * rhp_msg_t as one 16-byte load and walks its rhp_hdr_t records k < num_headers
+ * once (header-major: consecutive lanes read consecutive records) for the two
+ * framing names and the caller's together -- name_len against one length mask,
+ * the name's bytes only on a length match -- until all of them are settled;
+ * then the one value the decision needs.  Nothing of a message that is not
+ * ready, and no record k >= num_headers, is read; a message is ready only when
+ * [offsets[i], offsets[i] + ret) lies below `readable`, and every name and
+ * value read lies inside [0, ret). */
+__global__ __launch_bounds__(256) void rhp_frame_messages_kernel(FParams p)
+{
+  __shared__ uint32_t tab[kTabDwords];
+  __shared__ uint32_t lenmask[RHP_CLASSIFY_NAME_MAX + 1u];
+  {
+#if defined(__HIP_DEVICE_COMPILE__)   /* (as rhp_classify_kernel) */
+    const ka32 *ka = (const ka32 *) __builtin_amdgcn_kernarg_segment_ptr();
+#else
+    const ka32 *ka = nullptr;
+#endif
+    for (uint32_t t = threadIdx.x; t < kTabDwords; t += blockDim.x) tab[t] = ka[t];
+    if (threadIdx.x <= RHP_CLASSIFY_NAME_MAX) {
+      const ka32 *nl = ka + offsetof(CTables, name_len) / 4u;
+      uint32_t mk = (threadIdx.x == kTeLen ? kTeBit : 0u) | (threadIdx.x == kClLen ? kClBit : 0u);
+      for (uint32_t j = 0; j < p.n_names; j++) mk |= (((nl[j >> 2] >> (8u * (j & 3u))) & 0xffu) == threadIdx.x ? 1u : 0u) << j;
+      lenmask[threadIdx.x] = mk;
+    }
+  }
+  __syncthreads();
+
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = p.n;
+  if (i >= n) return;
+
+  /* ---- the message record: ready?  num_headers ---- */
+  const uint4 q = p.msgs[i];
+  const int32_t ret = (int32_t) q.x;
+  uint64_t at0 = 0;
+  bool ready = ret > 0;   /* RHP_RET_TOOLONG is negative */
+  if (ready) {
+    at0 = p.offsets[i];
+    ready = at0 <= p.readable && (uint64_t) (uint32_t) ret <= p.readable - at0;
+  }
+  uint32_t nh = ready ? q.w & 0xffffu : 0u;
+  if (nh > p.m) nh = p.m;   /* never more records than the batch holds */
+
+  /* ---- one walk: the framing names and the caller's ---- */
+  const uint32_t callers = (1u << p.n_names) - 1u, all = callers | kTeBit | kClBit;
+  const auto text_at = [](uint32_t j) { return j < RHP_CLASSIFY_MAX_NAMES ? j * kNameDwords : j == RHP_CLASSIFY_MAX_NAMES ? kTeAt : kClAt; };
+  uint32_t found = 0, te = 0, cl = 0;   /* te, cl: value_off | value_len << 16 of the first match */
+  for (uint32_t k = 0; k < nh && found != all; k++) {
+    const uint2 h = p.hdrs[(uint64_t) i * p.s_req + (uint64_t) k * p.s_hdr];
+    const uint32_t noff = h.x & 0xffffu, nl = h.x >> 16, voff = h.y & 0xffffu, vl = h.y >> 16;
+    if (noff == RHP_NAME_NULL) continue;   /* name == NULL: an obs-fold line */
+    uint32_t cand = nl <= RHP_CLASSIFY_NAME_MAX ? lenmask[nl] & ~found : 0u;
+    if (voff + vl > (uint32_t) ret) cand &= callers;   /* (a parsed value lies inside its header section) */
+    if (cand == 0) continue;
+    if (noff + nl > (uint32_t) ret) continue;          /* (and so does a parsed name) */
+    cand = same_text<true>(p.bytes + at0 + noff, nl, cand, tab, text_at);
+    for (uint32_t c = cand & callers; c; c &= c - 1u) p.fields[(uint64_t) __builtin_ctz(c) * n + i] = h.y;
+    if (cand & kTeBit) te = h.y;
+    if (cand & kClBit) cl = h.y;
+    found |= cand;
+  }
+  for (uint32_t c = callers & ~found; c; c &= c - 1u) p.fields[(uint64_t) __builtin_ctz(c) * n + i] = RHP_NAME_NULL;
+
+  /* ---- the decision (rhp_scalar.h frame_of_values) and the one value it reads ---- */
+  int32_t result = rhp::http_result_of(ret);   /* ret <= 0, or a message that does not lie inside the batch's bytes: 0 */
+  uint32_t kind = RHP_FRAME_NONE;
+  uint64_t body_len = 0;
+  if (ready) {
+    const uint32_t te_len = te >> 16, cl_len = cl >> 16;
+    bool chunked = false;
+    uint64_t number = 0;
+    if (cl_len) {
+      if (!te_len) number = value_number(p.bytes + at0 + (cl & 0xffffu), cl_len);
+    } else if (te_len == kChunkedLen) {
+      chunked = same_text<true>(p.bytes + at0 + (te & 0xffffu), kChunkedLen, 1u, tab, [](uint32_t) { return kChunkedAt; }) != 0;
+    }
+    result = rhp::frame_of_values(te_len, cl_len, chunked, number, &kind, &body_len);
+  }
+  p.frames[i] = uint4{(uint32_t) result, kind, (uint32_t) body_len, (uint32_t) (body_len >> 32)};
+  if (p.decoders && kind == RHP_FRAME_CHUNKED) p.decoders[i] = uint4{0u, 0u, p.consume_trailer, 0u};
+}
+
 }  // namespace
 
 extern "C" int rhp_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c, void *stream)
@@ -470,6 +619,37 @@ extern "C" int rhp_classify_sessions(const rhp_batch_t *b, const rhp_session_t *
   p.req_start = req_start;
   p.n_sessions = n_sessions;
   hipLaunchKernelGGL(rhp_classify_sessions_kernel, dim3((b->n + 255u) / 256u), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), p);
+  return (int) hipGetLastError();
+}
+
+extern "C" int rhp_frame_messages(const rhp_msg_batch_t *b, const rhp_frame_args_t *f, void *stream)
+{
+  const int rc = rhp_frame_check(b, f, 1);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const bool hmajor = b->layout == RHP_LAYOUT_HEADER_MAJOR;
+  FParams p;
+  const rhp_classify_t names = {f->text, f->names, nullptr, f->n_names, 0, nullptr, nullptr};
+  pack_tables(&names, p.t);
+  uint8_t *text = reinterpret_cast<uint8_t *>(p.t.text);
+  memcpy(text + 4u * (kTeAt - kTextAt), "TRANSFER-ENCODING", kTeLen);
+  memcpy(text + 4u * (kClAt - kTextAt), "CONTENT-LENGTH", kClLen);
+  memcpy(text + 4u * (kChunkedAt - kTextAt), "CHUNKED", kChunkedLen);
+  p.bytes = b->bytes;
+  p.offsets = b->offsets;
+  p.readable = rhp_frame_readable(b);
+  p.msgs = reinterpret_cast<const uint4 *>(b->msgs);
+  p.hdrs = reinterpret_cast<const uint2 *>(b->hdrs);
+  p.fields = reinterpret_cast<uint32_t *>(f->fields);
+  p.frames = reinterpret_cast<uint4 *>(f->frames);
+  p.decoders = reinterpret_cast<uint4 *>(f->decoders);
+  p.n = b->n;
+  p.m = b->max_headers;
+  p.n_names = f->n_names;
+  p.consume_trailer = f->consume_trailer;
+  p.s_req = hmajor ? 1u : b->max_headers;
+  p.s_hdr = hmajor ? b->n : 1u;
+  hipLaunchKernelGGL(rhp_frame_messages_kernel, dim3((uint32_t) (((uint64_t) b->n + 255u) / 256u)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), p);
   return (int) hipGetLastError();
 }

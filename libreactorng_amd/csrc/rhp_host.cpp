@@ -2,7 +2,7 @@
  * rhp_host.cpp -- the product's host entry points (rhp_host.h): the exact
  * scalar parser over a batch in host memory, the session fix-up, the dense
  * pack and the three expansions, the host classify, reply, gather and split, the
- * message parse (responses, header blocks), the chunked decoder, and the pointer-based
+ * message parse (responses, header blocks), their framing, the chunked decoder, and the pointer-based
  * rhp_phr_parse_request / _response / _headers, rhp_phr_decode_chunked and rhp_http_read_cpu.  libreactor.so links them.  The
  * parser is rhp_scalar.h's (the code the kernel's rare paths run); where the
  * records sit and how they are encoded is rhp_records.h's.
@@ -21,6 +21,7 @@
 #include "rhp_split_args.h"
 #include "rhp_msg_args.h"
 #include "rhp_chunked_args.h"
+#include "rhp_frame_args.h"
 #include "rhp_host_exact.h"
 
 using namespace rhp;
@@ -421,6 +422,65 @@ extern "C" int rhp_cpu_parse_messages(const rhp_msg_batch_t *b)
     OutMsg<PlainMsgStore> out{{b->msgs + i, b->hdrs ? b->hdrs + i * hs_req : nullptr, hs_hdr}};
     if (b->kind == RHP_MSG_RESPONSE) scalar_message_t<RHP_MSG_RESPONSE>(B, len, ll, b->max_headers, out);
     else scalar_message_t<RHP_MSG_HEADERS>(B, len, ll, b->max_headers, out);
+  }
+  return 0;
+}
+
+/* rhp_frame_messages (rhp.h) on the host, every pointer in host memory: per
+ * ready message the framing statement of rhp_scalar.h (frame_of_records_t) over
+ * a view of its records that hides what the kernel skips -- an obs-fold line, a
+ * record whose name or value does not lie inside [0, ret) -- and classify_one,
+ * the lookup both classify twins run, for the caller's names.  It shares the
+ * argument check with the launcher (rhp_frame_args.h). */
+namespace {
+
+/* HdrsRec (rhp_scalar.h) over records at any stride, inside [0, ret) */
+struct FrameHdrs {
+  const uint8_t *b;
+  const rhp_hdr_t *h;
+  uint64_t hs, ret;
+  const rhp_hdr_t &at(uint32_t i) const { return h[i * hs]; }
+  bool null(uint32_t i) const
+  {
+    const rhp_hdr_t &r = at(i);
+    return r.name_off == RHP_NAME_NULL || (uint64_t) r.name_off + r.name_len > ret || (uint64_t) r.value_off + r.value_len > ret;
+  }
+  const uint8_t *name(uint32_t i) const { return b + at(i).name_off; }
+  uint64_t name_len(uint32_t i) const { return at(i).name_len; }
+  const uint8_t *value(uint32_t i) const { return b + at(i).value_off; }
+  uint64_t value_len(uint32_t i) const { return at(i).value_len; }
+};
+
+}  // namespace
+
+extern "C" int rhp_cpu_frame_messages(const rhp_msg_batch_t *b, const rhp_frame_args_t *f)
+{
+  const int rc = rhp_frame_check(b, f, 0);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const uint32_t n = b->n, m = b->max_headers;
+  const bool hmajor = b->layout == RHP_LAYOUT_HEADER_MAJOR;
+  const uint64_t hs_req = hmajor ? 1u : m, hs_hdr = hmajor ? n : 1u, readable = rhp_frame_readable(b);
+  const rhp_classify_t c = {f->text, f->names, nullptr, f->n_names, 0, f->fields, nullptr};
+  for (uint32_t i = 0; i < n; i++) {
+    const int32_t ret = b->msgs[i].ret;
+    rhp_frame_t x = {http_result_of(ret), RHP_FRAME_NONE, 0};   /* (a ret > 0 that is not ready: 0) */
+    classify_absent(&c, n, i);
+    if (ret > 0 && b->offsets[i] <= readable && (uint64_t) ret <= readable - b->offsets[i]) {
+      const uint8_t *msg = b->bytes + b->offsets[i];
+      const rhp_hdr_t *h = b->hdrs ? b->hdrs + i * hs_req : nullptr;   /* (max_headers 0) */
+      const uint32_t nh = b->msgs[i].num_headers < m ? b->msgs[i].num_headers : m;
+      x.result = frame_of_records_t(FrameHdrs{msg, h, hs_hdr, (uint64_t) ret}, nh, &x.body_kind, &x.body_len);
+      rhp_req_t r = {};
+      r.ret = ret;
+      r.num_headers = (uint16_t) nh;
+      classify_one(&c, n, m, i, msg, r, [&](uint32_t k) -> const rhp_hdr_t & { return h[k * hs_hdr]; });
+      if (f->decoders && x.body_kind == RHP_FRAME_CHUNKED) {
+        rhp_chunked_t d = {};
+        d.consume_trailer = (uint8_t) f->consume_trailer;
+        f->decoders[i] = d;
+      }
+    }
+    f->frames[i] = x;
   }
   return 0;
 }

@@ -768,6 +768,56 @@ RHP_HD void http_frame(uint8_t *b, uint64_t len, const rhp_req_t &r, const rhp_h
  * on for the caller to parse it with a pointer-based parser */
 RHP_HD int32_t http_result_of(int n) { return n == kBad ? -1 : n == RHP_RET_TOOLONG ? RHP_RET_TOOLONG : 0; }
 
+/* ---- rhp_frame_messages (rhp.h): the framing of http.c:204-233 over the
+ * header records of a message, with no body looked at ---- */
+
+/* http.c:207-233 given what the two lookups returned: the lengths of the
+ * Transfer-Encoding and the Content-Length value (0: absent or empty), whether
+ * the first is `chunked`, and the second's strtoull.  The result; *kind and
+ * *body_len as rhp_frame_t has them.  The kernel (rhp_classify.hip) and the
+ * host twin decide here. */
+RHP_HD int32_t frame_of_values(uint32_t te_len, uint32_t cl_len, bool te_chunked, uint64_t cl_number, uint32_t *kind,
+                               uint64_t *body_len)
+{
+  *kind = RHP_FRAME_NONE;
+  *body_len = 0;
+  if (cl_len) {
+    if (te_len) return -1;
+    *kind = RHP_FRAME_LENGTH;
+    *body_len = cl_number;
+    return 1;
+  }
+  if (te_len) {
+    if (!te_chunked) return -1;
+    *kind = RHP_FRAME_CHUNKED;
+  }
+  return 1;
+}
+
+/* The framing decision for a record view (HdrsRec's members) of nh records:
+ * the two http_field_lookup calls (the first record whose name matches, whatever
+ * its value), data_equal_case against `chunked`, strtoull.  The host twin's
+ * statement; the kernel walks the records once for these two names and the
+ * caller's together, and shares frame_of_values, num_step and the folding. */
+template <class HV>
+RHP_HD int32_t frame_of_records_t(const HV &hv, uint32_t nh, uint32_t *kind, uint64_t *body_len)
+{
+  int te = -1, cl = -1;
+  for (uint32_t i = 0; i < nh && (te < 0 || cl < 0); i++) {
+    if (te < 0 && name_eq(hv, i, "Transfer-Encoding", 17)) te = (int) i;
+    if (cl < 0 && name_eq(hv, i, "Content-Length", 14)) cl = (int) i;
+  }
+  const uint64_t te_len = te >= 0 ? hv.value_len((uint32_t) te) : 0, cl_len = cl >= 0 ? hv.value_len((uint32_t) cl) : 0;
+  bool chunked = te_len == 7u;
+  if (chunked) {
+    const char *ch = "CHUNKED";
+    const uint8_t *v = hv.value((uint32_t) te);
+    for (uint32_t i = 0; i < 7; i++) chunked = chunked && upper(v[i]) == (uint32_t) ch[i];
+  }
+  const uint64_t number = cl_len ? strtoull10(hv.value((uint32_t) cl), cl_len) : 0;
+  return frame_of_values((uint32_t) te_len, (uint32_t) cl_len, chunked, number, kind, body_len);
+}
+
 /* Whole http_read_request for one request. */
 template <class Bytes, class DC = PlainDechunk>
 RHP_HD void scalar_http_t(Bytes &B, uint8_t *b, uint64_t len, uint32_t max, rhp_req_t *r, rhp_hdr_t *h, uint64_t hs,
