@@ -948,6 +948,127 @@ typedef struct rhp_frame_args {
 
 int rhp_frame_messages(const rhp_msg_batch_t *batch, const rhp_frame_args_t *f, void *stream);
 
+/*
+ * The three calls above as one loop per connection: the pipelined responses of
+ * n_sessions keep-alive upstream connections walked on the device.  The next
+ * response of a connection starts at start + ret + the body's length on the
+ * wire, known only when the one before it has been parsed and framed; the walk
+ * is that loop, sequential inside a session and parallel across sessions.
+ *   Session s is bytes[sess_off[s], sess_off[s+1]), a = sess_off[s], e =
+ *   sess_off[s+1]: the sessions lie back to back as for rhp_split_sessions,
+ *   sess_off is non-decreasing and RHP_PAD zero bytes follow the last session.
+ *   It owns the record slots [slot_off[s], slot_off[s+1]), slot_off
+ *   non-decreasing, slot_off[n_sessions] == n_slots_total.
+ *   The walk.  pos = a, slot = slot_off[s]; while pos < e:
+ *     no slot left: stop = RHP_WALK_MORE.
+ *     Parse.  RHP_MSG_RESPONSE of rhp_parse_messages for the message [pos, e)
+ *     with last_len 0 -- phr_parse_response(bytes + pos, e - pos, ...), with what
+ *     it reads past e (the next session's bytes, then the pad) -- into msgs[slot]
+ *     and hdrs[slot * max_headers + k]; slots[slot].start = pos.
+ *     ret == -2: result 0, stop = RHP_WALK_HEAD.  ret == -1: result -1, stop =
+ *     RHP_WALK_BAD.  RHP_RET_TOOLONG: result RHP_RET_TOOLONG, stop = RHP_WALK_BAD.
+ *     Framing.  rhp_frame_messages' rule over the records just written (first
+ *     match only, an empty value is absent, strtoull, `chunked`); its -1 gives
+ *     result -1, stop = RHP_WALK_BAD.
+ *     Body, with avail = e - (pos + ret):
+ *       A status of 100..199, 204 or 304 has no body whatever its headers say
+ *       (RFC 9112 section 6.3): body_kind stays what the framing said, body_len =
+ *       wire_len = 0.  THE REFERENCE HAS NO RULE HERE: this is the one rule of
+ *       the walk that is invented, not taken from it.
+ *       RHP_FRAME_LENGTH: body_len is the framing's value; body_len > avail
+ *       (compared as u64, nothing is added): wire_len = avail, stop =
+ *       RHP_WALK_BODY; otherwise wire_len = body_len.
+ *       RHP_FRAME_CHUNKED: phr_decode_chunked from a zero decoder, consume_trailer
+ *       = (flags & RHP_WALK_TRAILERS) != 0, over [pos + ret, e), no byte moved.
+ *       Its ret >= 0: body_len = *bufsz, wire_len = avail - ret.  -2: body_len =
+ *       *bufsz so far, wire_len = avail, stop = RHP_WALK_BODY.  -1: result -1,
+ *       stop = RHP_WALK_BAD.  With RHP_WALK_DEFRAME a body whose decode completed
+ *       is then de-framed in place: [pos + ret, pos + ret + wire_len) is left as
+ *       rhp_decode_chunked leaves that piece (body_len decoded bytes first).  A
+ *       partial or bad body is never touched.
+ *       RHP_FRAME_NONE on any other status: the body runs until the connection
+ *       closes: wire_len = avail, body_len = 0, stop = RHP_WALK_CLOSE.  With
+ *       RHP_WALK_NONE_EMPTY it is an empty body instead and the walk goes on.
+ *     A slot that stops the walk with HEAD or BAD has body_kind RHP_FRAME_NONE
+ *     and both lengths 0.  Every other slot has result 1; one that did not stop
+ *     the walk advances it: pos += ret + wire_len.  slot++.
+ *   The loop left with pos == e: stop = RHP_WALK_END.
+ *   results[s]: n_slots counts every written slot, the stopping one included;
+ *   consumed = pos - a counts complete messages only (the bytes of a BODY or
+ *   CLOSE slot are not in it).  An empty session: n_slots 0, RHP_WALK_END.
+ *   Slots at and past slot_off[s] + n_slots are not written, not even with
+ *   their own value.  A session whose slot_off pair is not ordered or reaches
+ *   beyond n_slots_total owns no slot: n_slots 0, RHP_WALK_MORE unless empty.
+ * Memory.  No byte at or beyond bytes + bytes_size is read, whatever sess_off
+ * holds: a session's ends are clamped to the readable end, bytes_size rounded
+ * down to whole 16-byte lines less one line (the de-framing move may load the
+ * line behind its last source byte); with RHP_PAD kept no session reaches it.
+ * The reader sees zeros from there on.  With sess_off not monotone or beyond
+ * bytes_size the answers are unspecified.  Stores: msgs, hdrs and slots of the
+ * written slots, results[0, n_sessions) and, with RHP_WALK_DEFRAME, bytes
+ * inside the wire span of a completed chunked body -- nothing else.  A message
+ * record and a result leave as one 16-byte store, a slot as two, a header
+ * record as one 8-byte store.
+ * Not here: a header lookup over walked slots (rhp_frame_messages addresses
+ * messages by offsets[i], not by slots[i].start); responses to HEAD requests
+ * (their framing headers describe a body that is not sent); resuming a partial
+ * chunked body across rounds (the caller hands [start + ret, e) and the later
+ * bytes to rhp_decode_chunked).
+ * -EINVAL (rhp_walk_args.h): a NULL w; max_headers above RHP_MAX_HEADERS; a
+ * flag bit that is not named here; n_slots_total * max_headers >= 2^32;
+ * RHP_WALK_DEFRAME with a bytes_rw that is NULL or not `bytes`; with
+ * n_sessions > 0: a NULL bytes, sess_off, slot_off or results; a NULL msgs or
+ * slots with n_slots_total > 0; a NULL hdrs with n_slots_total > 0 and
+ * max_headers > 0; bytes_size below RHP_PAD; bytes, msgs, slots or results not
+ * 16-byte aligned, hdrs not 8-byte aligned (the alignments: device pointers
+ * only).  n_sessions == 0 succeeds and launches nothing.
+ * Launch contract as rhp_parse_messages: one launch, asynchronous on `stream`,
+ * no allocation, no copy, no synchronisation; thread-safe.  One session per
+ * lane.
+ */
+enum rhp_walk_stop { RHP_WALK_END = 0,    /* the session's bytes are used up */
+                     RHP_WALK_HEAD,       /* the last slot's head is not complete (ret -2) */
+                     RHP_WALK_BAD,        /* the last slot is malformed (head, framing or chunk) or too long */
+                     RHP_WALK_BODY,       /* the last slot's body has not arrived in full */
+                     RHP_WALK_CLOSE,      /* the last slot's body runs until the connection closes */
+                     RHP_WALK_MORE };     /* the session's slots ran out with bytes left */
+
+#define RHP_WALK_TRAILERS   1u   /* chunked bodies: consume_trailer = 1 */
+#define RHP_WALK_DEFRAME    2u   /* de-frame completed chunked bodies in place (bytes_rw) */
+#define RHP_WALK_NONE_EMPTY 4u   /* RHP_FRAME_NONE on a status with a body: an empty body, the walk goes on */
+
+typedef struct rhp_walk_slot {    /* 32 B, leaves as two 16-byte stores */
+  uint64_t start;                 /* the message starts at bytes[start] */
+  uint64_t body_len;              /* LENGTH: the header's value; CHUNKED: decoded bytes (so far); else 0 */
+  uint64_t wire_len;              /* body bytes of this session's input: [start + ret, start + ret + wire_len) */
+  int32_t  result;                /* 1; 0 head incomplete; -1 malformed; RHP_RET_TOOLONG */
+  uint32_t body_kind;             /* RHP_FRAME_* */
+} rhp_walk_slot_t;
+
+typedef struct rhp_walk_result {  /* 16 B, leaves as one 16-byte store */
+  uint32_t n_slots;               /* slots written, the stopping one included */
+  uint32_t stop;                  /* enum rhp_walk_stop */
+  uint64_t consumed;              /* bytes of the complete messages, from the session's start */
+} rhp_walk_result_t;
+
+typedef struct rhp_walk_batch {
+  const uint8_t     *bytes;         /* device, 16-byte aligned */
+  uint8_t           *bytes_rw;      /* == bytes, writable: RHP_WALK_DEFRAME; otherwise may be NULL */
+  uint64_t           bytes_size;
+  const uint64_t    *sess_off;      /* device [n_sessions + 1] */
+  const uint64_t    *slot_off;      /* device [n_sessions + 1] */
+  uint32_t           n_sessions;
+  uint32_t           n_slots_total; /* host copy of slot_off[n_sessions] */
+  uint32_t           max_headers;   /* <= RHP_MAX_HEADERS, 0 allowed */
+  uint32_t           flags;         /* RHP_WALK_* */
+  rhp_msg_t         *msgs;          /* device [n_slots_total], 16-byte aligned */
+  rhp_hdr_t         *hdrs;          /* device [n_slots_total * max_headers], request-major; may be NULL when max_headers == 0 */
+  rhp_walk_slot_t   *slots;         /* device [n_slots_total], 16-byte aligned */
+  rhp_walk_result_t *results;       /* device [n_sessions], 16-byte aligned */
+} rhp_walk_batch_t;
+
+int rhp_walk_responses(const rhp_walk_batch_t *w, void *stream);
+
 
 #ifdef __cplusplus
 }

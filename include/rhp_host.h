@@ -147,6 +147,13 @@ int rhp_cpu_parse_messages(const rhp_msg_batch_t *batch);
  * [0, ret) are read. */
 int rhp_cpu_frame_messages(const rhp_msg_batch_t *batch, const rhp_frame_args_t *f);
 
+/* rhp_walk_responses (rhp.h) over sessions in host memory: every pointer of
+ * `w` is host memory, of any alignment, and there is no stream.  The same
+ * msgs, hdrs, slots, results and de-framed bytes and the same -22
+ * (rhp_walk_args.h; the alignment rules are the device's alone).  No byte at or
+ * beyond bytes + bytes_size is read. */
+int rhp_cpu_walk_responses(const rhp_walk_batch_t *w);
+
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */
 typedef struct rhp_phr_header {
   const char *name;

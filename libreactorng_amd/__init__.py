@@ -66,7 +66,8 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 # exported C-ABI symbols of librhp.so, as declared in include/rhp.h
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
                "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
-               "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages", "rhp_decode_chunked", "rhp_frame_messages")
+               "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages", "rhp_decode_chunked", "rhp_frame_messages",
+               "rhp_walk_responses")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
@@ -74,7 +75,7 @@ HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_spl
                 "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions", "rhp_cpu_gather_wide",
                 "rhp_cpu_split_sessions", "rhp_cpu_parse_messages", "rhp_phr_parse_response", "rhp_phr_parse_headers",
                 "rhp_cpu_decode_chunked", "rhp_phr_decode_chunked", "rhp_phr_decode_chunked_is_in_data",
-                "rhp_cpu_frame_messages")
+                "rhp_cpu_frame_messages", "rhp_cpu_walk_responses")
 
 _rhp = None
 _host = None
@@ -205,6 +206,23 @@ FRAME_DTYPE = np.dtype([("result", "<i4"), ("body_kind", "<u4"), ("body_len", "<
 assert FRAME_DTYPE.itemsize == 16 and ctypes.sizeof(FrameArgs) == 56
 
 
+class WalkBatch(ctypes.Structure):
+    """rhp_walk_batch_t (include/rhp.h): the sessions, slots and outputs of rhp_walk_responses"""
+    _fields_ = [("bytes", ctypes.c_void_p), ("bytes_rw", ctypes.c_void_p), ("bytes_size", ctypes.c_uint64),
+                ("sess_off", ctypes.c_void_p), ("slot_off", ctypes.c_void_p), ("n_sessions", ctypes.c_uint32),
+                ("n_slots_total", ctypes.c_uint32), ("max_headers", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("msgs", ctypes.c_void_p), ("hdrs", ctypes.c_void_p), ("slots", ctypes.c_void_p),
+                ("results", ctypes.c_void_p)]
+
+
+WALK_END, WALK_HEAD, WALK_BAD, WALK_BODY, WALK_CLOSE, WALK_MORE = range(6)   # enum rhp_walk_stop
+WALK_TRAILERS, WALK_DEFRAME, WALK_NONE_EMPTY = 1, 2, 4                       # RHP_WALK_* flags
+WALK_SLOT_DTYPE = np.dtype([("start", "<u8"), ("body_len", "<u8"), ("wire_len", "<u8"), ("result", "<i4"),
+                            ("body_kind", "<u4")])                           # rhp_walk_slot_t
+WALK_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("stop", "<u4"), ("consumed", "<u8")])   # rhp_walk_result_t
+assert WALK_SLOT_DTYPE.itemsize == 32 and WALK_RESULT_DTYPE.itemsize == 16 and ctypes.sizeof(WalkBatch) == 88
+
+
 def _torch_hip_runtime() -> str | None:
     """Path of the HIP runtime torch ships (torch/lib/libamdhip64.so), found
     without importing torch."""
@@ -289,6 +307,8 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_decode_chunked.restype = ctypes.c_int
         _rhp.rhp_frame_messages.argtypes = [ctypes.POINTER(MsgBatch), ctypes.POINTER(FrameArgs), vp]
         _rhp.rhp_frame_messages.restype = ctypes.c_int
+        _rhp.rhp_walk_responses.argtypes = [ctypes.POINTER(WalkBatch), vp]
+        _rhp.rhp_walk_responses.restype = ctypes.c_int
     return _rhp
 
 
@@ -359,6 +379,8 @@ def host() -> ctypes.CDLL:
         _host.rhp_phr_decode_chunked_is_in_data.restype = ctypes.c_int
         _host.rhp_cpu_frame_messages.argtypes = [ctypes.POINTER(MsgBatch), ctypes.POINTER(FrameArgs)]
         _host.rhp_cpu_frame_messages.restype = ctypes.c_int
+        _host.rhp_cpu_walk_responses.argtypes = [ctypes.POINTER(WalkBatch)]
+        _host.rhp_cpu_walk_responses.restype = ctypes.c_int
     return _host
 
 
@@ -2028,3 +2050,84 @@ def frame_messages_gpu(buf, off, kind: int, names=(), max_headers: int = 16, lay
         for g in (db, gf, gl) + ((gd,) if decoders else ()):
             g.check()
     return _frame_result(gf.view.cpu().numpy(), gl.view.cpu().numpy(), gd.view.cpu().numpy() if decoders else None, n, nn)
+
+
+# The three calls above as one loop per connection (rhp.h rhp_walk_responses): the pipelined responses of a
+# batch of keep-alive upstream connections, parsed, framed and stepped over on the device.
+
+WALK_POISON = 0xC3   # what msgs, hdrs, slots and results hold before a call (tests): no answer's value
+
+
+def _walk_result(results, slots, msgs, hdrs, bytes_out, n_sessions, n_slots, max_headers):
+    """(results WALK_RESULT_DTYPE [n_sessions], slots WALK_SLOT_DTYPE [n_slots], msgs MSG_DTYPE [n_slots], hdrs
+    HDR_DTYPE [n_slots, max_headers], the bytes as the call left them) from the bytes of the outputs"""
+    return (results[: 16 * n_sessions].view(WALK_RESULT_DTYPE), slots[: 32 * n_slots].view(WALK_SLOT_DTYPE),
+            msgs[: 16 * n_slots].view(MSG_DTYPE), hdrs[: 8 * n_slots * max_headers].view(HDR_DTYPE).reshape(n_slots, max_headers),
+            bytes_out)
+
+
+def walk_responses_cpu(buf, sess_off, slot_off, max_headers: int = 16, flags: int = 0, bytes_size: int | None = None,
+                       n_slots_total: int | None = None):
+    """rhp_cpu_walk_responses (include/rhp_host.h): `buf` the sessions back to back with RHP_PAD zero bytes
+    behind them (u8), sess_off and slot_off u64 [n_sessions + 1].  Nothing passed in is changed.  bytes_size: what
+    the batch states (default: all of buf); n_slots_total: the host's copy (default: slot_off[-1]).  Returns
+    (results, slots, msgs, hdrs, bytes) as _walk_result; the four records held WALK_POISON before the call."""
+    buf = np.array(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    ns = len(sess_off) - 1
+    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    res = np.full(max(16 * ns, 1), WALK_POISON, dtype=np.uint8)
+    slots = np.full(max(32 * nt, 1), WALK_POISON, dtype=np.uint8)
+    msgs = np.full(max(16 * nt, 1), WALK_POISON, dtype=np.uint8)
+    hdrs = np.full(max(8 * nt * max_headers, 1), WALK_POISON, dtype=np.uint8)
+    w = WalkBatch(_ptr(buf), _ptr(buf), buf.size if bytes_size is None else bytes_size, _ptr(sess_off), _ptr(slot_off), ns,
+                  nt, max_headers, flags, _ptr(msgs), _ptr(hdrs), _ptr(slots), _ptr(res))
+    rc = host().rhp_cpu_walk_responses(ctypes.byref(w))
+    if rc != 0:
+        raise RuntimeError(f"rhp_cpu_walk_responses failed: {rc}")
+    return _walk_result(res, slots, msgs, hdrs, buf, ns, nt, max_headers)
+
+
+def walk_responses_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sessions: int, n_slots_total: int,
+                          max_headers: int, flags: int, msgs_t, hdrs_t, slots_t, results_t, stream=None):
+    """One rhp_walk_responses call over device tensors on the stream (default: the current one): bytes_t u8
+    (16-byte aligned; written with WALK_DEFRAME), sess_off_t and slot_off_t i64 / u64 [n_sessions + 1]; the
+    records are left in msgs_t (u8, 16 * n_slots_total bytes), hdrs_t (u8, 8 * n_slots_total * max_headers bytes;
+    None when max_headers == 0), slots_t (u8, 32 * n_slots_total bytes) and results_t (u8, 16 * n_sessions bytes).
+    Nothing is synchronised or copied: the tensors are the call's only inputs and outputs."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    w = WalkBatch(_addr(bytes_t), _addr(bytes_t), bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions,
+                  n_slots_total, max_headers, flags, _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+    rc = lib().rhp_walk_responses(ctypes.byref(w), ctypes.c_void_p(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_walk_responses failed: {rc}")
+
+
+def walk_responses_gpu(buf, sess_off, slot_off, max_headers: int = 16, flags: int = 0, guard: int = 0,
+                       fill: int = WALK_POISON, bytes_size: int | None = None, n_slots_total: int | None = None):
+    """The sessions walked on the GPU.  bytes, msgs, hdrs, slots and results are Guarded device buffers (guard
+    bytes on both sides, checked after the call); the four records hold `fill` first.  Returns what
+    walk_responses_cpu returns."""
+    import torch
+    buf = np.array(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    ns = len(sess_off) - 1
+    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    db = Guarded("bytes", buf.size, guard, data=buf)
+    gm = Guarded("msgs", max(16 * nt, 1), guard, fill=fill)
+    gh = Guarded("hdrs", max(8 * nt * max_headers, 1), guard, fill=fill)
+    gs = Guarded("slots", max(32 * nt, 1), guard, fill=fill)
+    gr = Guarded("results", max(16 * ns, 1), guard, fill=fill)
+    dso = torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda")
+    dsl = torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda")
+    walk_responses_device(db.view, buf.size if bytes_size is None else bytes_size, dso, dsl, ns, nt, max_headers, flags,
+                          gm.view, gh.view, gs.view, gr.view)
+    torch.cuda.synchronize()
+    if guard:
+        for g in (db, gm, gh, gs, gr):
+            g.check()
+    return _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
+                        db.view.cpu().numpy(), ns, nt, max_headers)

@@ -2,7 +2,7 @@
  * rhp_host.cpp -- the product's host entry points (rhp_host.h): the exact
  * scalar parser over a batch in host memory, the session fix-up, the dense
  * pack and the three expansions, the host classify, reply, gather and split, the
- * message parse (responses, header blocks), their framing, the chunked decoder, and the pointer-based
+ * message parse (responses, header blocks), their framing, the chunked decoder, the response walk, and the pointer-based
  * rhp_phr_parse_request / _response / _headers, rhp_phr_decode_chunked and rhp_http_read_cpu.  libreactor.so links them.  The
  * parser is rhp_scalar.h's (the code the kernel's rare paths run); where the
  * records sit and how they are encoded is rhp_records.h's.
@@ -22,6 +22,7 @@
 #include "rhp_msg_args.h"
 #include "rhp_chunked_args.h"
 #include "rhp_frame_args.h"
+#include "rhp_walk_args.h"
 #include "rhp_host_exact.h"
 
 using namespace rhp;
@@ -537,6 +538,54 @@ extern "C" ssize_t rhp_phr_decode_chunked(rhp_chunked_t *decoder, char *buf, siz
 extern "C" int rhp_phr_decode_chunked_is_in_data(rhp_chunked_t *decoder)
 {
   return decoder->state == RHP_CHUNKED_IN_CHUNK_DATA;   /* picohttpparser.c:638-641 */
+}
+
+/* rhp_walk_responses (rhp.h) on the host, every pointer in host memory: the
+ * kernel's statement (rhp_scalar.h walk_session_t) session by session, with the
+ * launcher's argument check and the kernel's two clamps (rhp_walk_args.h).  The
+ * reader is bounded as the kernel's is: zeros from the readable end on. */
+namespace {
+
+struct BoundedPlainBytes {
+  const uint8_t *bytes;
+  uint64_t at, size;
+  uint32_t operator()(uint64_t p) const { return at + p < size ? bytes[at + p] : 0u; }
+};
+
+struct HostWalkIO {
+  const rhp_walk_batch_t *w;
+  uint64_t lim;
+  BoundedPlainBytes bytes(uint64_t at) const { return BoundedPlainBytes{w->bytes, at, lim}; }
+  PlainMsgStore store(uint32_t slot) const
+  {
+    return PlainMsgStore{w->msgs + slot, w->hdrs ? w->hdrs + (uint64_t) slot * w->max_headers : nullptr, 1};
+  }
+  HdrsRec hdrs(uint32_t slot, uint64_t at) const
+  {
+    return HdrsRec{w->bytes + at, w->hdrs ? w->hdrs + (uint64_t) slot * w->max_headers : nullptr, 1};
+  }
+  PlainMove move(uint64_t at) const { return PlainMove{w->bytes_rw + at}; }
+  void slot(uint32_t slot, const rhp_walk_slot_t &x) const { w->slots[slot] = x; }
+};
+
+}  // namespace
+
+extern "C" int rhp_cpu_walk_responses(const rhp_walk_batch_t *w)
+{
+  const int rc = rhp_walk_check(w, 0);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  HostWalkIO io{w, rhp_walk_readable(w->bytes_size)};
+  for (uint32_t s = 0; s < w->n_sessions; s++) {
+    uint64_t a = w->sess_off[s], e = w->sess_off[s + 1];
+    a = a < io.lim ? a : io.lim;
+    e = e < a ? a : e < io.lim ? e : io.lim;
+    uint64_t lo = w->slot_off[s], hi = w->slot_off[s + 1];
+    if (lo > hi || hi > w->n_slots_total) hi = lo = 0;   /* owns no slot */
+    rhp_walk_result_t r;
+    walk_session_t(io, a, e, (uint32_t) lo, (uint32_t) hi, w->max_headers, w->flags, &r);
+    w->results[s] = r;
+  }
+  return 0;
 }
 
 /* ---- the pointer-based host parser: phr_parse_request's own outputs ---- */

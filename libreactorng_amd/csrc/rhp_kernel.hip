@@ -38,6 +38,7 @@
 
 #include "rhp.h"
 #include "rhp_records.h"
+#include "rhp_device.h"
 #include "rhp_dfa.h"
 #include "rhp_scalar.h"
 
@@ -353,77 +354,7 @@ struct LineBytes {
   }
 };
 
-/* n body bytes from src to dst (dst <= src, offsets from `in`), forward: the
- * in-place move of http_dechunk (http.c:155) for one thread.  Destination
- * blocks are whole aligned 16-byte stores built from aligned 16-byte source
- * lines (funnel-shifted by the constant src - dst), four blocks per memory
- * round trip; the partial first and last blocks are byte stores, so no byte
- * outside [dst, dst + n) -- another request's -- is written.  Loads read only
- * source bytes no earlier store has reached (each block's source lies past its
- * destination), apart from unused bytes of shared lines. */
-struct DevMove {
-  uint8_t *in;
-  __device__ void operator()(uint64_t dst, uint64_t src, uint64_t n) const
-  {
-    typedef __attribute__((address_space(1))) const u32x4 gq;
-    typedef __attribute__((address_space(1))) u32x4 gw;
-    if (n == 0 || dst == src) return;
-    const uintptr_t da = (uintptr_t) (in + dst), de = da + n, delta = (uintptr_t) (src - dst);
-    const uint32_t q = (uint32_t) (delta >> 2) & 3u, r = (uint32_t) delta & 3u;
-    /* block at destination A: source bytes [A + delta, A + delta + 16) from the
-     * lines at (A + delta) & ~15 and the one after it */
-    auto ld = [](uintptr_t a) -> u32x4 { return *reinterpret_cast<gq *>(a); };
-    auto block = [&](const u32x4 &l0, const u32x4 &l1) {
-      const uint32_t w[8] = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-      u32x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint32_t lo = q == 0 ? w[j] : q == 1 ? w[j + 1] : q == 2 ? w[j + 2] : w[j + 3];
-        const uint32_t hi = q == 0 ? w[j + 1] : q == 1 ? w[j + 2] : q == 2 ? w[j + 3] : w[j + 4];
-        o[j] = __builtin_amdgcn_alignbyte(hi, lo, r);
-      }
-      return o;
-    };
-    auto partial = [&](uintptr_t A) {   /* bytes of block A inside [da, de): whole dwords, then bytes */
-      typedef __attribute__((address_space(1))) uint32_t gw1;
-      typedef __attribute__((address_space(1))) uint8_t gb1;
-      const uintptr_t s0 = (A + delta) & ~(uintptr_t) 15;
-      const u32x4 o = block(ld(s0), ld(s0 + 16));
-#pragma unroll
-      for (uint32_t j = 0; j < 4; j++) {
-        const uintptr_t w = A + 4 * j;
-        if (w >= da && w + 4 <= de) {
-          *reinterpret_cast<gw1 *>(w) = o[j];
-        } else if (w + 4 > da && w < de) {
-#pragma unroll
-          for (uint32_t k = 0; k < 4; k++)
-            if (w + k >= da && w + k < de) *reinterpret_cast<gb1 *>(w + k) = (uint8_t) (o[j] >> (8 * k));
-        }
-      }
-    };
-    uintptr_t A = da & ~(uintptr_t) 15;
-    if (A != da || A + 16 > de) {   /* a partial first block */
-      partial(A);
-      A += 16;
-    }
-    constexpr int U = 4;   /* destination blocks per memory round trip */
-    while (A + 16 * U <= de) {
-      const uintptr_t s0 = (A + delta) & ~(uintptr_t) 15;
-      u32x4 l[U + 1];
-#pragma unroll
-      for (int u = 0; u <= U; u++) l[u] = ld(s0 + 16 * u);
-#pragma unroll
-      for (int u = 0; u < U; u++) *reinterpret_cast<gw *>(A + 16 * u) = block(l[u], l[u + 1]);
-      A += 16 * U;
-    }
-    while (A + 16 <= de) {
-      const uintptr_t s0 = (A + delta) & ~(uintptr_t) 15;
-      *reinterpret_cast<gw *>(A) = block(ld(s0), ld(s0 + 16));
-      A += 16;
-    }
-    if (A < de) partial(A);
-  }
-};
+using rhp_device::DevMove;   /* http_dechunk's in-place move for one thread */
 
 /* http_dechunk on the GPU (rhp_scalar.h dechunk_t): size lines read through the
  * 16-byte line cache, payloads moved 16 bytes per store */

@@ -32,7 +32,8 @@
 namespace {
 
 using namespace rhp;
-using rhp_device::u32x4;
+using rhp_device::BoundedLineBytes;
+using rhp_device::DevMsgStore;
 
 struct MParams {
   const uint8_t  *bytes;
@@ -42,48 +43,6 @@ struct MParams {
   rhp_hdr_t      *hdrs;
   uint32_t        n, max_headers;
   uint32_t        hs_req, hs_hdr;   /* record k of message i at hdrs[i * hs_req + k * hs_hdr] */
-};
-
-/* byte p of the message that starts at byte `at` of the batch (bytes is
- * 16-byte aligned: a line is an aligned 16-byte load) */
-struct BoundedLineBytes {
-  const uint8_t *bytes;
-  uint64_t at, size, line;   /* size: a multiple of 16 */
-  u32x4 c;
-  __device__ uint32_t operator()(uint64_t p)
-  {
-    const uint64_t a = at + p;
-    const uint64_t l = a & ~(uint64_t) 15;
-    if (l != line) {
-      c = u32x4{0, 0, 0, 0};
-      if (l < size) c = *reinterpret_cast<const __attribute__((address_space(1))) u32x4 *>((uintptr_t) (bytes + l));
-      line = l;
-    }
-    const uint32_t q = (uint32_t) (a >> 2) & 3u;
-    const uint32_t d = q == 0 ? c[0] : q == 1 ? c[1] : q == 2 ? c[2] : c[3];
-    return (d >> (8u * ((uint32_t) a & 3u))) & 0xffu;
-  }
-};
-
-/* OutMsg's Store on the device: whole records, one store each */
-struct DevMsgStore {
-  rhp_msg_t *m;
-  rhp_hdr_t *h;
-  uint64_t hs;
-  __device__ void msg(const rhp_msg_t &v) const
-  {
-    static_assert(sizeof(rhp_msg_t) == 16, "a message record is one 16-byte store");
-    u32x4 w;
-    __builtin_memcpy(&w, &v, 16);
-    *reinterpret_cast<u32x4 *>(m) = w;
-  }
-  __device__ void hdr(uint32_t k, const rhp_hdr_t &v) const
-  {
-    static_assert(sizeof(rhp_hdr_t) == 8, "a header record is one 8-byte store");
-    uint2 w;
-    __builtin_memcpy(&w, &v, 8);
-    *reinterpret_cast<uint2 *>(h + k * hs) = w;
-  }
 };
 
 template <uint32_t KIND>

@@ -1021,6 +1021,113 @@ RHP_HD int64_t decode_chunked_t(Bytes &B, Move &move, uint64_t len, bool consume
   return ret;
 }
 
+/* ---- rhp_walk_responses (rhp.h): the pipelined responses of one session ---- */
+
+/* decode_chunked_t's Move for a dry run: its reads never depend on its moves,
+ * so ret and *size are the reference's with no byte moved */
+struct NoMove {
+  RHP_HDM void operator()(uint64_t, uint64_t, uint64_t) const {}
+};
+
+/* OutMsg's Store for the walk: the message record leaves through st and stays
+ * here for the framing and the status rule */
+template <class Store>
+struct WalkStore {
+  Store st;
+  rhp_msg_t m;
+  RHP_HDM void msg(const rhp_msg_t &v)
+  {
+    m = v;
+    st.msg(v);
+  }
+  RHP_HDM void hdr(uint32_t k, const rhp_hdr_t &v) { st.hdr(k, v); }
+};
+
+/* RFC 9112 6.3: a 1xx, 204 or 304 response has no body whatever its headers
+ * say.  The reference has no rule for it; the walk's one invented rule. */
+RHP_HD bool status_has_no_body(uint32_t status) { return status - 100u < 100u || status == 204u || status == 304u; }
+
+/* The walk of rhp.h over the session [a, e) (both clamped by the caller) that
+ * owns the slots [slot_lo, slot_hi): one phr_parse_response, one framing
+ * decision (frame_of_records_t) and, for a chunked body, one phr_decode_chunked
+ * from a zero decoder per message, advancing by what they consumed.  io says
+ * where bytes and records live:
+ *   io.bytes(at)      a byte reader, B(p) = bytes[at + p]
+ *   io.store(slot)    OutMsg's Store for the slot's message and header records
+ *   io.hdrs(slot, at) a record view (HdrsRec's members) of the slot's header
+ *                     records as just written, for the message at `at`
+ *   io.move(at)       decode_chunked_t's Move over the bytes at `at` (RHP_WALK_DEFRAME)
+ *   io.slot(slot, x)  slots[slot] = x
+ * The kernel (rhp_walk.hip) and the host twin (rhp_host.cpp) instantiate it. */
+template <class IO>
+RHP_HD void walk_session_t(IO &io, uint64_t a, uint64_t e, uint32_t slot_lo, uint32_t slot_hi, uint32_t max_headers,
+                           uint32_t flags, rhp_walk_result_t *out)
+{
+  const bool trailers = (flags & RHP_WALK_TRAILERS) != 0;
+  uint64_t pos = a;
+  uint32_t slot = slot_lo, stop = RHP_WALK_END;
+  while (pos < e) {
+    if (slot == slot_hi) {
+      stop = RHP_WALK_MORE;
+      break;
+    }
+    rhp_walk_slot_t x;
+    x.start = pos; x.body_len = 0; x.wire_len = 0; x.result = 1; x.body_kind = RHP_FRAME_NONE;
+    auto B = io.bytes(pos);
+    OutMsg<WalkStore<decltype(io.store(slot))>> o{{io.store(slot), {}}};
+    const int ret = scalar_response_t(B, e - pos, max_headers, o);
+    if (ret <= 0) {
+      x.result = http_result_of(ret);
+      stop = ret == kPartial ? RHP_WALK_HEAD : RHP_WALK_BAD;
+    } else {
+      const uint64_t body = pos + (uint64_t) ret, avail = e - body;
+      x.result = frame_of_records_t(io.hdrs(slot, pos), o.st.m.num_headers, &x.body_kind, &x.body_len);
+      if (x.result != 1) {
+        stop = RHP_WALK_BAD;   /* (frame_of_values left RHP_FRAME_NONE, 0) */
+      } else if (status_has_no_body(o.st.m.status)) {
+        x.body_len = 0;
+      } else if (x.body_kind == RHP_FRAME_LENGTH) {
+        x.wire_len = x.body_len > avail ? avail : x.body_len;
+        if (x.body_len > avail) stop = RHP_WALK_BODY;
+      } else if (x.body_kind == RHP_FRAME_CHUNKED) {
+        auto C = io.bytes(body);
+        NoMove dry;
+        uint64_t left = 0, size = 0;
+        uint32_t hex = 0, st = RHP_CHUNKED_IN_CHUNK_SIZE;
+        const int64_t r = decode_chunked_t(C, dry, avail, trailers, left, hex, st, &size);
+        if (r == kBad) {
+          x.result = -1;
+          x.body_kind = RHP_FRAME_NONE;
+          stop = RHP_WALK_BAD;
+        } else if (r < 0) {
+          x.body_len = size;
+          x.wire_len = avail;
+          stop = RHP_WALK_BODY;
+        } else {
+          x.body_len = size;
+          x.wire_len = avail - (uint64_t) r;
+          if (flags & RHP_WALK_DEFRAME) {   /* the same decode over the body's own wire span, moving */
+            auto D = io.bytes(body);
+            auto M = io.move(body);
+            left = 0; hex = 0; st = RHP_CHUNKED_IN_CHUNK_SIZE;
+            (void) decode_chunked_t(D, M, x.wire_len, trailers, left, hex, st, &size);
+          }
+        }
+      } else if (!(flags & RHP_WALK_NONE_EMPTY)) {
+        x.wire_len = avail;
+        stop = RHP_WALK_CLOSE;
+      }
+      if (stop == RHP_WALK_END) pos = body + x.wire_len;
+    }
+    io.slot(slot, x);
+    slot++;
+    if (stop != RHP_WALK_END) break;
+  }
+  out->n_slots = slot - slot_lo;
+  out->stop = stop;
+  out->consumed = pos - a;
+}
+
 }  // namespace rhp
 
 #endif

@@ -1,0 +1,44 @@
+/*
+ * rhp_walk_args.h -- the argument rules of rhp_walk_responses (rhp.h), one
+ * statement of them for the kernel's launcher (rhp_walk.hip) and the host twin
+ * (rhp_host.cpp rhp_cpu_walk_responses), with the two clamps both apply to
+ * whatever sess_off and slot_off hold.
+ */
+#ifndef RHP_WALK_ARGS_H
+#define RHP_WALK_ARGS_H
+
+#include <stdint.h>
+#include "rhp.h"
+
+#define RHP_WALK_FLAGS (RHP_WALK_TRAILERS | RHP_WALK_DEFRAME | RHP_WALK_NONE_EMPTY)
+
+/* 0: walk the sessions; 1: nothing to do (n_sessions == 0); -22: refused.
+ * device_pointers adds the launcher's own rules (the reader's lines are aligned
+ * 16-byte loads, the records leave as whole 16- and 8-byte stores), which host
+ * callers, who pass any memory, leave out. */
+static inline int rhp_walk_check(const rhp_walk_batch_t *w, int device_pointers)
+{
+  if (!w) return -22;
+  if (w->max_headers > RHP_MAX_HEADERS) return -22;
+  if (w->flags & ~RHP_WALK_FLAGS) return -22;
+  if ((uint64_t) w->n_slots_total * w->max_headers > 0xffffffffull) return -22;   /* record indices are 32-bit */
+  if ((w->flags & RHP_WALK_DEFRAME) && (!w->bytes_rw || w->bytes_rw != w->bytes)) return -22;   /* the same bytes, writable */
+  if (w->n_sessions == 0) return 1;
+  if (!w->bytes || !w->sess_off || !w->slot_off || !w->results) return -22;
+  if (w->n_slots_total > 0 && (!w->msgs || !w->slots)) return -22;
+  if (w->n_slots_total > 0 && w->max_headers > 0 && !w->hdrs) return -22;
+  if (w->bytes_size < RHP_PAD) return -22;   /* bytes_size >= sess_off[n_sessions] + RHP_PAD */
+  if (device_pointers &&
+      ((((uintptr_t) w->bytes | (uintptr_t) w->msgs | (uintptr_t) w->slots | (uintptr_t) w->results) & 15u) != 0 ||
+       ((uintptr_t) w->hdrs & 7u) != 0))
+    return -22;
+  return 0;
+}
+
+/* where a session has to end, and where the reader's zeros begin: bytes_size
+ * rounded down to whole 16-byte lines, less one line -- the de-framing move
+ * loads the aligned line behind the one that holds its last source byte.  A
+ * batch that keeps RHP_PAD has no session beyond it (RHP_PAD >= 31). */
+static inline uint64_t rhp_walk_readable(uint64_t bytes_size) { return (bytes_size & ~(uint64_t) 15) - 16u; }
+
+#endif
