@@ -1012,8 +1012,8 @@ int rhp_frame_messages(const rhp_msg_batch_t *batch, const rhp_frame_args_t *f, 
  * Not here: a header lookup over walked slots (rhp_frame_messages addresses
  * messages by offsets[i], not by slots[i].start); responses to HEAD requests
  * (their framing headers describe a body that is not sent); resuming a partial
- * chunked body across rounds (the caller hands [start + ret, e) and the later
- * bytes to rhp_decode_chunked).
+ * chunked body across rounds (rhp_walk_resume, below, carries the walk from
+ * round to round).
  * -EINVAL (rhp_walk_args.h): a NULL w; max_headers above RHP_MAX_HEADERS; a
  * flag bit that is not named here; n_slots_total * max_headers >= 2^32;
  * RHP_WALK_DEFRAME with a bytes_rw that is NULL or not `bytes`; with
@@ -1068,6 +1068,91 @@ typedef struct rhp_walk_batch {
 } rhp_walk_batch_t;
 
 int rhp_walk_responses(const rhp_walk_batch_t *w, void *stream);
+
+/*
+ * The walk above carried across rounds.  An upstream connection does not
+ * deliver whole responses per round: a round ends inside a Content-Length body,
+ * inside a chunk, inside a size line, inside a head.  states[s], 32 bytes that
+ * stay in HBM, say where session s stands between rounds: read at entry,
+ * written at exit, all zero before the connection's first round.  The batch,
+ * the flags, the clamps and the memory contract are rhp_walk_responses'.
+ *   A round's input.  Session s's bytes [a, e) of a round are the bytes the
+ *   round before left unconsumed, [a + consumed, e) of that round, with the
+ *   newly arrived bytes behind them.  The unconsumed bytes are not empty only
+ *   after RHP_WALK_HEAD (the incomplete head) and RHP_WALK_MORE.
+ *   On an all-zero state the call is rhp_walk_responses but for two things,
+ *   both because the bytes of a body that has started are taken:
+ *     1. a slot that stops with RHP_WALK_BODY or RHP_WALK_CLOSE sets pos = e, so
+ *        consumed = e - a counts the head and the body bytes that are there, and
+ *        the state is armed (below): the next round starts inside the body;
+ *     2. with RHP_WALK_DEFRAME a partial chunked body (the RHP_WALK_BODY slot)
+ *        is de-framed too: [body, body + wire_len) is left as rhp_decode_chunked
+ *        leaves that piece from that decoder -- body_len decoded bytes first,
+ *        behind them every byte keeps its value.
+ *   One round of session s:
+ *   1. Corrupt or dead state: phase >= RHP_WALK_DEAD, reserved != 0, or
+ *      RHP_WALK_IN_CHUNKED with decoder.state > 5 or decoder.hex_count > 16:
+ *      n_slots 0, stop RHP_WALK_BAD, consumed 0; the state keeps its value, no
+ *      byte is read or written.
+ *   2. Empty round, a == e: n_slots 0, consumed 0, the state is kept; stop is
+ *      RHP_WALK_END at AT_HEAD, RHP_WALK_BODY at IN_LENGTH and IN_CHUNKED,
+ *      RHP_WALK_CLOSE at IN_CLOSE.
+ *   3. Continuation, an IN_* phase and a < e.  With no slot left: RHP_WALK_MORE,
+ *      consumed 0, the state is kept, nothing is touched.  Otherwise the
+ *      session's first slot is a continuation slot: start = a, result = 1,
+ *      msgs[slot] sixteen zero bytes, no header record written.  (A slot with
+ *      result == 1 and msgs[slot].ret == 0 is a continuation; a head slot with
+ *      result == 1 has ret > 0.)
+ *        IN_LENGTH: body_kind LENGTH, body_len = left at entry, wire_len =
+ *        min(left, e - a), left -= wire_len; left != 0: stop RHP_WALK_BODY;
+ *        otherwise the walk goes on at a + wire_len from AT_HEAD.
+ *        IN_CHUNKED: phr_decode_chunked from states[s].decoder over [a, e), with
+ *        the decoder's own consume_trailer; body_kind CHUNKED, body_len = *bufsz.
+ *        ret >= 0: wire_len = (e - a) - ret, on from AT_HEAD.  -2: wire_len =
+ *        e - a, stop RHP_WALK_BODY, the decoder saved as it was left.  -1:
+ *        result -1, body_kind NONE, both lengths 0, stop RHP_WALK_BAD, no byte
+ *        touched.  With RHP_WALK_DEFRAME [a, a + wire_len) is de-framed as in 2
+ *        above, unless the answer is -1.
+ *        IN_CLOSE: body_kind NONE, body_len 0, wire_len = e - a, stop
+ *        RHP_WALK_CLOSE.
+ *   4. Heads: rhp_walk_responses' loop from there, with the two differences.
+ *      Arming: IN_LENGTH with left = body_len - avail; IN_CHUNKED with the
+ *      decoder as the decode over [body, e) left it, started from a zero decoder
+ *      with consume_trailer = (flags & RHP_WALK_TRAILERS) != 0 (a head that ends
+ *      exactly at e: the zero decoder, wire_len 0); IN_CLOSE.
+ *   5. The state at exit, written whole: phase AT_HEAD after RHP_WALK_END, HEAD
+ *      and MORE; IN_LENGTH / IN_CHUNKED after RHP_WALK_BODY; IN_CLOSE after
+ *      RHP_WALK_CLOSE; DEAD after RHP_WALK_BAD (consumed still counts the
+ *      complete messages before it).  left is 0 unless IN_LENGTH, the decoder
+ *      zero unless IN_CHUNKED, reserved 0.
+ *   results[s].consumed counts, from a: the continuation's wire_len, every
+ *   complete message, and the head and body bytes of a BODY or CLOSE slot.
+ * Memory as rhp_walk_responses; in addition states[s] is loaded and stored as
+ * two 16-byte accesses each, and with RHP_WALK_DEFRAME bytes inside the wire
+ * span of a partial chunked body are written too.  A session's answers do not
+ * depend on its neighbours' bytes, moved or not: the one read past e that can
+ * reach them is the SP run behind the version, and a run that reaches e gives
+ * -2 whatever lies beyond.
+ * -EINVAL (rhp_walk_args.h): whatever rhp_walk_responses refuses; with
+ * n_sessions > 0 a NULL states; states not 16-byte aligned (device pointers
+ * only).  n_sessions == 0 succeeds and launches nothing.
+ * Launch contract as rhp_walk_responses: one launch, one session per lane,
+ * asynchronous on `stream`, no allocation, no copy, no synchronisation.
+ */
+enum rhp_walk_phase { RHP_WALK_AT_HEAD = 0,   /* the round's first byte starts a head */
+                      RHP_WALK_IN_LENGTH,     /* inside a Content-Length body: `left` bytes still to come */
+                      RHP_WALK_IN_CHUNKED,    /* inside a chunked body: `decoder` is where it stands */
+                      RHP_WALK_IN_CLOSE,      /* inside a body that runs until the connection closes */
+                      RHP_WALK_DEAD };        /* a round stopped with RHP_WALK_BAD */
+
+typedef struct rhp_walk_state {   /* 32 B, two 16-byte accesses; all zero before a connection's first round */
+  rhp_chunked_t decoder;          /* as rhp_decode_chunked carries it */
+  uint64_t      left;
+  uint32_t      phase;            /* enum rhp_walk_phase */
+  uint32_t      reserved;         /* 0 */
+} rhp_walk_state_t;
+
+int rhp_walk_resume(const rhp_walk_batch_t *w, rhp_walk_state_t *states /* device [n_sessions], 16-byte aligned */, void *stream);
 
 
 #ifdef __cplusplus

@@ -154,6 +154,13 @@ int rhp_cpu_frame_messages(const rhp_msg_batch_t *batch, const rhp_frame_args_t 
  * beyond bytes + bytes_size is read. */
 int rhp_cpu_walk_responses(const rhp_walk_batch_t *w);
 
+/* rhp_walk_resume (rhp.h) over sessions and states in host memory, of any
+ * alignment, with no stream: one round, states[s] read at entry and written at
+ * exit.  The same msgs, hdrs, slots, results, states and de-framed bytes and
+ * the same -22 (rhp_walk_args.h; the alignment rules are the device's alone).
+ * Sequential; a caller with threads hands each a range of sessions. */
+int rhp_cpu_walk_resume(const rhp_walk_batch_t *w, rhp_walk_state_t *states);
+
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */
 typedef struct rhp_phr_header {
   const char *name;

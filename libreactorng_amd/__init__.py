@@ -67,7 +67,7 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
                "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
                "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages", "rhp_decode_chunked", "rhp_frame_messages",
-               "rhp_walk_responses")
+               "rhp_walk_responses", "rhp_walk_resume")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
@@ -75,7 +75,7 @@ HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_spl
                 "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions", "rhp_cpu_gather_wide",
                 "rhp_cpu_split_sessions", "rhp_cpu_parse_messages", "rhp_phr_parse_response", "rhp_phr_parse_headers",
                 "rhp_cpu_decode_chunked", "rhp_phr_decode_chunked", "rhp_phr_decode_chunked_is_in_data",
-                "rhp_cpu_frame_messages", "rhp_cpu_walk_responses")
+                "rhp_cpu_frame_messages", "rhp_cpu_walk_responses", "rhp_cpu_walk_resume")
 
 _rhp = None
 _host = None
@@ -221,6 +221,9 @@ WALK_SLOT_DTYPE = np.dtype([("start", "<u8"), ("body_len", "<u8"), ("wire_len", 
                             ("body_kind", "<u4")])                           # rhp_walk_slot_t
 WALK_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("stop", "<u4"), ("consumed", "<u8")])   # rhp_walk_result_t
 assert WALK_SLOT_DTYPE.itemsize == 32 and WALK_RESULT_DTYPE.itemsize == 16 and ctypes.sizeof(WalkBatch) == 88
+WALK_AT_HEAD, WALK_IN_LENGTH, WALK_IN_CHUNKED, WALK_IN_CLOSE, WALK_DEAD = range(5)   # enum rhp_walk_phase
+WALK_STATE_DTYPE = np.dtype([("decoder", CHUNKED_DTYPE), ("left", "<u8"), ("phase", "<u4"), ("reserved", "<u4")])   # rhp_walk_state_t
+assert WALK_STATE_DTYPE.itemsize == 32
 
 
 def _torch_hip_runtime() -> str | None:
@@ -309,6 +312,8 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_frame_messages.restype = ctypes.c_int
         _rhp.rhp_walk_responses.argtypes = [ctypes.POINTER(WalkBatch), vp]
         _rhp.rhp_walk_responses.restype = ctypes.c_int
+        _rhp.rhp_walk_resume.argtypes = [ctypes.POINTER(WalkBatch), vp, vp]
+        _rhp.rhp_walk_resume.restype = ctypes.c_int
     return _rhp
 
 
@@ -381,6 +386,8 @@ def host() -> ctypes.CDLL:
         _host.rhp_cpu_frame_messages.restype = ctypes.c_int
         _host.rhp_cpu_walk_responses.argtypes = [ctypes.POINTER(WalkBatch)]
         _host.rhp_cpu_walk_responses.restype = ctypes.c_int
+        _host.rhp_cpu_walk_resume.argtypes = [ctypes.POINTER(WalkBatch), vp]
+        _host.rhp_cpu_walk_resume.restype = ctypes.c_int
     return _host
 
 
@@ -2131,3 +2138,85 @@ def walk_responses_gpu(buf, sess_off, slot_off, max_headers: int = 16, flags: in
             g.check()
     return _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
                         db.view.cpu().numpy(), ns, nt, max_headers)
+
+
+# The walk carried across rounds (rhp.h rhp_walk_resume): `states` (WALK_STATE_DTYPE [n_sessions], all zero before a
+# connection's first round) goes in and comes out; a round's input is what the round before left unconsumed and the
+# new bytes behind it.
+
+
+def _walk_states(states, n_sessions):
+    """a private, contiguous copy of the states as u8 (32 bytes each); None: all zero"""
+    if states is None:
+        return np.zeros(max(32 * n_sessions, 1), dtype=np.uint8)
+    st = np.ascontiguousarray(states).view(np.uint8).reshape(-1).copy()
+    assert st.size == 32 * n_sessions, "one rhp_walk_state_t per session"
+    return st if st.size else np.zeros(1, dtype=np.uint8)
+
+
+def walk_resume_cpu(buf, sess_off, slot_off, states=None, max_headers: int = 16, flags: int = 0, bytes_size: int | None = None,
+                    n_slots_total: int | None = None):
+    """rhp_cpu_walk_resume (include/rhp_host.h): one round.  Arguments as walk_responses_cpu, and `states`
+    (WALK_STATE_DTYPE [n_sessions]; None: all zero).  Nothing passed in is changed.  Returns (results, slots, msgs,
+    hdrs, bytes, states): walk_responses_cpu's five and the states the round left."""
+    buf = np.array(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    ns = len(sess_off) - 1
+    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    st = _walk_states(states, ns)
+    res = np.full(max(16 * ns, 1), WALK_POISON, dtype=np.uint8)
+    slots = np.full(max(32 * nt, 1), WALK_POISON, dtype=np.uint8)
+    msgs = np.full(max(16 * nt, 1), WALK_POISON, dtype=np.uint8)
+    hdrs = np.full(max(8 * nt * max_headers, 1), WALK_POISON, dtype=np.uint8)
+    w = WalkBatch(_ptr(buf), _ptr(buf), buf.size if bytes_size is None else bytes_size, _ptr(sess_off), _ptr(slot_off), ns,
+                  nt, max_headers, flags, _ptr(msgs), _ptr(hdrs), _ptr(slots), _ptr(res))
+    rc = host().rhp_cpu_walk_resume(ctypes.byref(w), _ptr(st))
+    if rc != 0:
+        raise RuntimeError(f"rhp_cpu_walk_resume failed: {rc}")
+    return _walk_result(res, slots, msgs, hdrs, buf, ns, nt, max_headers) + (st[: 32 * ns].view(WALK_STATE_DTYPE),)
+
+
+def walk_resume_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sessions: int, n_slots_total: int,
+                       max_headers: int, flags: int, msgs_t, hdrs_t, slots_t, results_t, states_t, stream=None):
+    """One rhp_walk_resume call over device tensors on the stream (default: the current one): the tensors of
+    walk_responses_device, and states_t (u8, 32 * n_sessions bytes, 16-byte aligned), read at entry and written at
+    exit.  It stays on the device: a chain of rounds hands the same tensor to every call.  Nothing is synchronised
+    or copied."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    w = WalkBatch(_addr(bytes_t), _addr(bytes_t), bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions,
+                  n_slots_total, max_headers, flags, _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+    rc = lib().rhp_walk_resume(ctypes.byref(w), _addr(states_t), ctypes.c_void_p(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_walk_resume failed: {rc}")
+
+
+def walk_resume_gpu(buf, sess_off, slot_off, states=None, max_headers: int = 16, flags: int = 0, guard: int = 0,
+                    fill: int = WALK_POISON, bytes_size: int | None = None, n_slots_total: int | None = None):
+    """One round on the GPU.  bytes, msgs, hdrs, slots, results and states are Guarded device buffers (guard bytes
+    on both sides, checked after the call); the four records hold `fill` first.  `states`: WALK_STATE_DTYPE
+    [n_sessions] (None: all zero), or a Guarded buffer an earlier round returned, which is used as it lies on the
+    device.  Returns what walk_resume_cpu returns, and behind it the Guarded states buffer for the next round."""
+    import torch
+    buf = np.array(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    ns = len(sess_off) - 1
+    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    db = Guarded("bytes", buf.size, guard, data=buf)
+    gm = Guarded("msgs", max(16 * nt, 1), guard, fill=fill)
+    gh = Guarded("hdrs", max(8 * nt * max_headers, 1), guard, fill=fill)
+    gs = Guarded("slots", max(32 * nt, 1), guard, fill=fill)
+    gr = Guarded("results", max(16 * ns, 1), guard, fill=fill)
+    gt = states if isinstance(states, Guarded) else Guarded("states", max(32 * ns, 1), guard, data=_walk_states(states, ns))
+    dso = torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda")
+    dsl = torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda")
+    walk_resume_device(db.view, buf.size if bytes_size is None else bytes_size, dso, dsl, ns, nt, max_headers, flags,
+                       gm.view, gh.view, gs.view, gr.view, gt.view)
+    torch.cuda.synchronize()
+    if guard:
+        for g in (db, gm, gh, gs, gr, gt):
+            g.check()
+    return _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
+                        db.view.cpu().numpy(), ns, nt, max_headers) + (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE), gt)

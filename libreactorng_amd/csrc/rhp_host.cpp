@@ -588,6 +588,28 @@ extern "C" int rhp_cpu_walk_responses(const rhp_walk_batch_t *w)
   return 0;
 }
 
+/* rhp_walk_resume (rhp.h) on the host: walk_resume_t over the same io, with
+ * the launcher's argument check and the kernel's clamps */
+extern "C" int rhp_cpu_walk_resume(const rhp_walk_batch_t *w, rhp_walk_state_t *states)
+{
+  const int rc = rhp_walk_resume_check(w, states, 0);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  HostWalkIO io{w, rhp_walk_readable(w->bytes_size)};
+  for (uint32_t s = 0; s < w->n_sessions; s++) {
+    uint64_t a = w->sess_off[s], e = w->sess_off[s + 1];
+    a = a < io.lim ? a : io.lim;
+    e = e < a ? a : e < io.lim ? e : io.lim;
+    uint64_t lo = w->slot_off[s], hi = w->slot_off[s + 1];
+    if (lo > hi || hi > w->n_slots_total) hi = lo = 0;   /* owns no slot */
+    rhp_walk_state_t st;
+    memcpy(&st, &states[s], sizeof st);   /* (any alignment) */
+    rhp_walk_result_t r;
+    if (walk_resume_t(io, a, e, (uint32_t) lo, (uint32_t) hi, w->max_headers, w->flags, &st, &r)) memcpy(&states[s], &st, sizeof st);
+    w->results[s] = r;
+  }
+  return 0;
+}
+
 /* ---- the pointer-based host parser: phr_parse_request's own outputs ---- */
 
 namespace {

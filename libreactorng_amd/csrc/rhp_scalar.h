@@ -1047,85 +1047,250 @@ struct WalkStore {
  * say.  The reference has no rule for it; the walk's one invented rule. */
 RHP_HD bool status_has_no_body(uint32_t status) { return status - 100u < 100u || status == 204u || status == 304u; }
 
-/* The walk of rhp.h over the session [a, e) (both clamped by the caller) that
- * owns the slots [slot_lo, slot_hi): one phr_parse_response, one framing
- * decision (frame_of_records_t) and, for a chunked body, one phr_decode_chunked
- * from a zero decoder per message, advancing by what they consumed.  io says
- * where bytes and records live:
+/* What a walk that takes the bytes of a started body (rhp_walk_resume) has to
+ * remember of it: the phase the next round starts in and, of a Content-Length
+ * body, the bytes still to come, of a chunked one the decoder's fields as
+ * decode_chunked_t left them. */
+struct WalkCarry {
+  uint32_t phase;             /* enum rhp_walk_phase */
+  uint32_t consume_trailer;   /* IN_CHUNKED: the decoder's consume_trailer byte */
+  uint64_t left;              /* IN_LENGTH */
+  uint64_t chunk_left;        /* IN_CHUNKED: bytes_left_in_chunk, hex_count, state */
+  uint32_t hex, st;
+};
+
+/* One message of the walk of rhp.h, at pos, into `slot`: one phr_parse_response,
+ * one framing decision (frame_of_records_t) and, for a chunked body, one
+ * phr_decode_chunked from a zero decoder; pos advances by what they consumed.
+ * Returns the stop code, RHP_WALK_END when the walk goes on.  TAKE is
+ * rhp_walk_resume's difference: a body that has started is taken -- pos = e on
+ * RHP_WALK_BODY and RHP_WALK_CLOSE, `c` says where the body stands, and with
+ * RHP_WALK_DEFRAME the part of a chunked body that is there is de-framed too.
+ * Without TAKE `c` is not touched.  io says where bytes and records live:
  *   io.bytes(at)      a byte reader, B(p) = bytes[at + p]
  *   io.store(slot)    OutMsg's Store for the slot's message and header records
  *   io.hdrs(slot, at) a record view (HdrsRec's members) of the slot's header
  *                     records as just written, for the message at `at`
  *   io.move(at)       decode_chunked_t's Move over the bytes at `at` (RHP_WALK_DEFRAME)
- *   io.slot(slot, x)  slots[slot] = x
- * The kernel (rhp_walk.hip) and the host twin (rhp_host.cpp) instantiate it. */
-template <class IO>
-RHP_HD void walk_session_t(IO &io, uint64_t a, uint64_t e, uint32_t slot_lo, uint32_t slot_hi, uint32_t max_headers,
-                           uint32_t flags, rhp_walk_result_t *out)
+ *   io.slot(slot, x)  slots[slot] = x */
+template <bool TAKE, class IO>
+RHP_HD uint32_t walk_message_t(IO &io, uint64_t &pos, uint64_t e, uint32_t slot, uint32_t max_headers, uint32_t flags,
+                               WalkCarry &c)
 {
   const bool trailers = (flags & RHP_WALK_TRAILERS) != 0;
-  uint64_t pos = a;
-  uint32_t slot = slot_lo, stop = RHP_WALK_END;
+  uint32_t stop = RHP_WALK_END;
+  rhp_walk_slot_t x;
+  x.start = pos; x.body_len = 0; x.wire_len = 0; x.result = 1; x.body_kind = RHP_FRAME_NONE;
+  auto B = io.bytes(pos);
+  OutMsg<WalkStore<decltype(io.store(slot))>> o{{io.store(slot), {}}};
+  const int ret = scalar_response_t(B, e - pos, max_headers, o);
+  if (ret <= 0) {
+    x.result = http_result_of(ret);
+    stop = ret == kPartial ? RHP_WALK_HEAD : RHP_WALK_BAD;
+  } else {
+    const uint64_t body = pos + (uint64_t) ret, avail = e - body;
+    x.result = frame_of_records_t(io.hdrs(slot, pos), o.st.m.num_headers, &x.body_kind, &x.body_len);
+    if (x.result != 1) {
+      stop = RHP_WALK_BAD;   /* (frame_of_values left RHP_FRAME_NONE, 0) */
+    } else if (status_has_no_body(o.st.m.status)) {
+      x.body_len = 0;
+    } else if (x.body_kind == RHP_FRAME_LENGTH) {
+      x.wire_len = x.body_len > avail ? avail : x.body_len;
+      if (x.body_len > avail) {
+        stop = RHP_WALK_BODY;
+        if (TAKE) {
+          c.phase = RHP_WALK_IN_LENGTH;
+          c.left = x.body_len - avail;
+        }
+      }
+    } else if (x.body_kind == RHP_FRAME_CHUNKED) {
+      auto C = io.bytes(body);
+      NoMove dry;
+      uint64_t left = 0, size = 0;
+      uint32_t hex = 0, st = RHP_CHUNKED_IN_CHUNK_SIZE;
+      const int64_t r = decode_chunked_t(C, dry, avail, trailers, left, hex, st, &size);
+      auto deframe = [&](uint64_t wire) {   /* the same decode over the body's own wire span, moving */
+        auto D = io.bytes(body);
+        auto M = io.move(body);
+        uint64_t l = 0, sz = 0;
+        uint32_t h = 0, s = RHP_CHUNKED_IN_CHUNK_SIZE;
+        (void) decode_chunked_t(D, M, wire, trailers, l, h, s, &sz);
+      };
+      if (r == kBad) {
+        x.result = -1;
+        x.body_kind = RHP_FRAME_NONE;
+        stop = RHP_WALK_BAD;
+      } else if (r < 0) {
+        x.body_len = size;
+        x.wire_len = avail;
+        stop = RHP_WALK_BODY;
+        if (TAKE) {
+          c.phase = RHP_WALK_IN_CHUNKED;
+          c.consume_trailer = trailers;
+          c.chunk_left = left;
+          c.hex = hex;
+          c.st = st;
+          if (flags & RHP_WALK_DEFRAME) deframe(x.wire_len);   /* what is there of it */
+        }
+      } else {
+        x.body_len = size;
+        x.wire_len = avail - (uint64_t) r;
+        if (flags & RHP_WALK_DEFRAME) deframe(x.wire_len);
+      }
+    } else if (!(flags & RHP_WALK_NONE_EMPTY)) {
+      x.wire_len = avail;
+      stop = RHP_WALK_CLOSE;
+      if (TAKE) c.phase = RHP_WALK_IN_CLOSE;
+    }
+    if (stop == RHP_WALK_END) pos = body + x.wire_len;
+    else if (TAKE && (stop == RHP_WALK_BODY || stop == RHP_WALK_CLOSE)) pos = e;
+  }
+  io.slot(slot, x);
+  return stop;
+}
+
+/* the walk's loop over heads from pos on: a message per slot until the bytes,
+ * the slots or a stop end it */
+template <bool TAKE, class IO>
+RHP_HD uint32_t walk_heads_t(IO &io, uint64_t &pos, uint64_t e, uint32_t &slot, uint32_t slot_hi, uint32_t max_headers,
+                             uint32_t flags, WalkCarry &c)
+{
+  uint32_t stop = RHP_WALK_END;
   while (pos < e) {
     if (slot == slot_hi) {
       stop = RHP_WALK_MORE;
       break;
     }
-    rhp_walk_slot_t x;
-    x.start = pos; x.body_len = 0; x.wire_len = 0; x.result = 1; x.body_kind = RHP_FRAME_NONE;
-    auto B = io.bytes(pos);
-    OutMsg<WalkStore<decltype(io.store(slot))>> o{{io.store(slot), {}}};
-    const int ret = scalar_response_t(B, e - pos, max_headers, o);
-    if (ret <= 0) {
-      x.result = http_result_of(ret);
-      stop = ret == kPartial ? RHP_WALK_HEAD : RHP_WALK_BAD;
-    } else {
-      const uint64_t body = pos + (uint64_t) ret, avail = e - body;
-      x.result = frame_of_records_t(io.hdrs(slot, pos), o.st.m.num_headers, &x.body_kind, &x.body_len);
-      if (x.result != 1) {
-        stop = RHP_WALK_BAD;   /* (frame_of_values left RHP_FRAME_NONE, 0) */
-      } else if (status_has_no_body(o.st.m.status)) {
-        x.body_len = 0;
-      } else if (x.body_kind == RHP_FRAME_LENGTH) {
-        x.wire_len = x.body_len > avail ? avail : x.body_len;
-        if (x.body_len > avail) stop = RHP_WALK_BODY;
-      } else if (x.body_kind == RHP_FRAME_CHUNKED) {
-        auto C = io.bytes(body);
-        NoMove dry;
-        uint64_t left = 0, size = 0;
-        uint32_t hex = 0, st = RHP_CHUNKED_IN_CHUNK_SIZE;
-        const int64_t r = decode_chunked_t(C, dry, avail, trailers, left, hex, st, &size);
-        if (r == kBad) {
-          x.result = -1;
-          x.body_kind = RHP_FRAME_NONE;
-          stop = RHP_WALK_BAD;
-        } else if (r < 0) {
-          x.body_len = size;
-          x.wire_len = avail;
-          stop = RHP_WALK_BODY;
-        } else {
-          x.body_len = size;
-          x.wire_len = avail - (uint64_t) r;
-          if (flags & RHP_WALK_DEFRAME) {   /* the same decode over the body's own wire span, moving */
-            auto D = io.bytes(body);
-            auto M = io.move(body);
-            left = 0; hex = 0; st = RHP_CHUNKED_IN_CHUNK_SIZE;
-            (void) decode_chunked_t(D, M, x.wire_len, trailers, left, hex, st, &size);
-          }
-        }
-      } else if (!(flags & RHP_WALK_NONE_EMPTY)) {
-        x.wire_len = avail;
-        stop = RHP_WALK_CLOSE;
-      }
-      if (stop == RHP_WALK_END) pos = body + x.wire_len;
-    }
-    io.slot(slot, x);
+    stop = walk_message_t<TAKE>(io, pos, e, slot, max_headers, flags, c);
     slot++;
     if (stop != RHP_WALK_END) break;
   }
+  return stop;
+}
+
+/* The walk of rhp.h (rhp_walk_responses) over the session [a, e) (both clamped
+ * by the caller) that owns the slots [slot_lo, slot_hi).  The kernel
+ * (rhp_walk.hip) and the host twin (rhp_host.cpp) instantiate it. */
+template <class IO>
+RHP_HD void walk_session_t(IO &io, uint64_t a, uint64_t e, uint32_t slot_lo, uint32_t slot_hi, uint32_t max_headers,
+                           uint32_t flags, rhp_walk_result_t *out)
+{
+  uint64_t pos = a;
+  uint32_t slot = slot_lo;
+  WalkCarry none;   /* (never touched) */
+  const uint32_t stop = walk_heads_t<false>(io, pos, e, slot, slot_hi, max_headers, flags, none);
   out->n_slots = slot - slot_lo;
   out->stop = stop;
   out->consumed = pos - a;
+}
+
+/* ---- rhp_walk_resume (rhp.h): the walk of one session, carried across rounds ---- */
+
+/* One round of the session [a, e) from *state (a copy the caller loaded): the
+ * continuation slot of a body that an earlier round left open, then
+ * walk_heads_t taking the bytes of a started body.  Returns whether *state,
+ * rewritten whole, is to be stored: not for a corrupt or dead state, an empty
+ * round or a continuation with no slot, which keep the state as it lies. */
+template <class IO>
+RHP_HD bool walk_resume_t(IO &io, uint64_t a, uint64_t e, uint32_t slot_lo, uint32_t slot_hi, uint32_t max_headers,
+                          uint32_t flags, rhp_walk_state_t *state, rhp_walk_result_t *out)
+{
+  const uint32_t phase = state->phase;
+  out->n_slots = 0;
+  out->consumed = 0;
+  if (phase >= RHP_WALK_DEAD || state->reserved != 0 ||
+      (phase == RHP_WALK_IN_CHUNKED &&
+       (state->decoder.state > RHP_CHUNKED_IN_TRAILERS_LINE_MIDDLE || state->decoder.hex_count > 16u))) {
+    out->stop = RHP_WALK_BAD;
+    return false;
+  }
+  if (a == e) {
+    out->stop = phase == RHP_WALK_AT_HEAD ? RHP_WALK_END : phase == RHP_WALK_IN_CLOSE ? RHP_WALK_CLOSE : RHP_WALK_BODY;
+    return false;
+  }
+  uint64_t pos = a;
+  uint32_t slot = slot_lo, stop = RHP_WALK_END;
+  WalkCarry c;
+  c.phase = RHP_WALK_AT_HEAD; c.consume_trailer = 0; c.left = 0; c.chunk_left = 0; c.hex = 0; c.st = 0;
+  rhp_chunked_t dec = {};   /* the decoder a chunked body leaves: a continuation's own, a head's zero one */
+  if (phase != RHP_WALK_AT_HEAD) {
+    if (slot == slot_hi) {
+      out->stop = RHP_WALK_MORE;
+      return false;
+    }
+    const uint64_t avail = e - a;
+    rhp_walk_slot_t x;
+    x.start = a; x.body_len = 0; x.wire_len = 0; x.result = 1; x.body_kind = RHP_FRAME_NONE;
+    const rhp_msg_t none = {};
+    io.store(slot).msg(none);   /* ret 0: a continuation, no head */
+    if (phase == RHP_WALK_IN_LENGTH) {
+      x.body_kind = RHP_FRAME_LENGTH;
+      x.body_len = state->left;
+      x.wire_len = x.body_len > avail ? avail : x.body_len;
+      if (x.body_len > avail) {
+        stop = RHP_WALK_BODY;
+        c.phase = RHP_WALK_IN_LENGTH;
+        c.left = x.body_len - avail;
+      }
+    } else if (phase == RHP_WALK_IN_CHUNKED) {
+      dec = state->decoder;
+      const bool trailers = dec.consume_trailer != 0;
+      auto C = io.bytes(a);
+      NoMove dry;
+      uint64_t left = dec.bytes_left_in_chunk, size = 0;
+      uint32_t hex = dec.hex_count, st = dec.state;
+      const int64_t r = decode_chunked_t(C, dry, avail, trailers, left, hex, st, &size);
+      if (r == kBad) {
+        x.result = -1;
+        stop = RHP_WALK_BAD;
+      } else {
+        x.body_kind = RHP_FRAME_CHUNKED;
+        x.body_len = size;
+        if (r < 0) {
+          x.wire_len = avail;
+          stop = RHP_WALK_BODY;
+          c.phase = RHP_WALK_IN_CHUNKED;
+          c.consume_trailer = dec.consume_trailer;
+          c.chunk_left = left;
+          c.hex = hex;
+          c.st = st;
+        } else {
+          x.wire_len = avail - (uint64_t) r;
+          dec = rhp_chunked_t{};
+        }
+        if (flags & RHP_WALK_DEFRAME) {   /* the same decode from the same decoder over the wire span, moving */
+          auto D = io.bytes(a);
+          auto M = io.move(a);
+          left = state->decoder.bytes_left_in_chunk; hex = state->decoder.hex_count; st = state->decoder.state;
+          (void) decode_chunked_t(D, M, x.wire_len, trailers, left, hex, st, &size);
+        }
+      }
+    } else {
+      x.wire_len = avail;
+      stop = RHP_WALK_CLOSE;
+      c.phase = RHP_WALK_IN_CLOSE;
+    }
+    pos = a + x.wire_len;
+    io.slot(slot, x);
+    slot++;
+  }
+  if (stop == RHP_WALK_END) stop = walk_heads_t<true>(io, pos, e, slot, slot_hi, max_headers, flags, c);
+  if (stop == RHP_WALK_BAD) c.phase = RHP_WALK_DEAD;
+  rhp_walk_state_t n = {};
+  n.phase = c.phase;
+  if (c.phase == RHP_WALK_IN_LENGTH) n.left = c.left;
+  if (c.phase == RHP_WALK_IN_CHUNKED) {
+    n.decoder = dec;
+    n.decoder.bytes_left_in_chunk = c.chunk_left;
+    n.decoder.consume_trailer = (uint8_t) c.consume_trailer;
+    n.decoder.hex_count = (uint8_t) c.hex;
+    n.decoder.state = (uint8_t) c.st;
+  }
+  *state = n;
+  out->n_slots = slot - slot_lo;
+  out->stop = stop;
+  out->consumed = pos - a;
+  return true;
 }
 
 }  // namespace rhp

@@ -1,6 +1,7 @@
 /*
  * rhp_walk.hip -- rhp_walk_responses (rhp.h): the pipelined responses of a
- * batch of upstream connections walked in HBM.  gfx950.
+ * batch of upstream connections walked in HBM, and rhp_walk_resume, the same
+ * walk carried from round to round by a 32-byte state per session.  gfx950.
  *
  * One session per lane, one launch: the lane runs the walk's one statement
  * (rhp_scalar.h walk_session_t) -- the code the host twin runs over plain
@@ -118,12 +119,49 @@ __global__ __launch_bounds__(256) void rhp_walk_kernel(WParams p)
   *reinterpret_cast<u32x4 *>(p.results + s) = w;
 }
 
+/* rhp_walk_resume: the same lane per session over walk_resume_t, from
+ * states[s] (two 16-byte loads) to states[s] (two 16-byte stores, none where
+ * the statement keeps the state as it lies).  A continuation reads and moves
+ * from the session's first byte on, with the reader and the move of the walk
+ * above: nothing loaded at or behind the readable end, nothing stored outside
+ * [a, e). */
+struct RParams {
+  WParams w;
+  rhp_walk_state_t *states;
+};
+
+__global__ __launch_bounds__(256) void rhp_walk_resume_kernel(RParams q)
+{
+  const WParams &p = q.w;
+  const uint64_t t = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+  if (t >= p.n_sessions) return;
+  const uint32_t s = (uint32_t) t;
+  uint64_t a = p.sess_off[s], e = p.sess_off[s + 1];
+  a = a < p.lim ? a : p.lim;
+  e = e < a ? a : e < p.lim ? e : p.lim;
+  uint64_t lo = p.slot_off[s], hi = p.slot_off[s + 1];
+  if (lo > hi || hi > p.n_slots_total) hi = lo = 0;   /* owns no slot */
+  static_assert(sizeof(rhp_walk_state_t) == 32, "a state is two 16-byte accesses");
+  u32x4 *sp = reinterpret_cast<u32x4 *>(q.states + s);
+  u32x4 sw[2] = {sp[0], sp[1]};
+  rhp_walk_state_t st;
+  __builtin_memcpy(&st, sw, 32);
+  DevWalkIO io{p};
+  rhp_walk_result_t r;
+  if (walk_resume_t(io, a, e, (uint32_t) lo, (uint32_t) hi, p.max_headers, p.flags, &st, &r)) {
+    __builtin_memcpy(sw, &st, 32);
+    sp[0] = sw[0];
+    sp[1] = sw[1];
+  }
+  u32x4 w;
+  __builtin_memcpy(&w, &r, 16);
+  *reinterpret_cast<u32x4 *>(p.results + s) = w;
+}
+
 }  // namespace
 
-extern "C" int rhp_walk_responses(const rhp_walk_batch_t *b, void *stream)
+static WParams walk_params(const rhp_walk_batch_t *b)
 {
-  const int rc = rhp_walk_check(b, 1);
-  if (rc != 0) return rc < 0 ? rc : 0;
   WParams p;
   p.bytes = b->bytes;
   p.bytes_rw = b->bytes_rw;
@@ -138,8 +176,27 @@ extern "C" int rhp_walk_responses(const rhp_walk_batch_t *b, void *stream)
   p.n_slots_total = b->n_slots_total;
   p.max_headers = b->max_headers;
   p.flags = b->flags;
+  return p;
+}
+
+extern "C" int rhp_walk_responses(const rhp_walk_batch_t *b, void *stream)
+{
+  const int rc = rhp_walk_check(b, 1);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const WParams p = walk_params(b);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((uint32_t) (((uint64_t) b->n_sessions + 255u) / 256u));
   hipLaunchKernelGGL(rhp_walk_kernel, grid, dim3(256), 0, s, p);
+  return (int) hipGetLastError();
+}
+
+extern "C" int rhp_walk_resume(const rhp_walk_batch_t *b, rhp_walk_state_t *states, void *stream)
+{
+  const int rc = rhp_walk_resume_check(b, states, 1);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const RParams q = {walk_params(b), states};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((uint32_t) (((uint64_t) b->n_sessions + 255u) / 256u));
+  hipLaunchKernelGGL(rhp_walk_resume_kernel, grid, dim3(256), 0, s, q);
   return (int) hipGetLastError();
 }

@@ -1,8 +1,9 @@
 /*
- * rhp_walk_args.h -- the argument rules of rhp_walk_responses (rhp.h), one
- * statement of them for the kernel's launcher (rhp_walk.hip) and the host twin
- * (rhp_host.cpp rhp_cpu_walk_responses), with the two clamps both apply to
- * whatever sess_off and slot_off hold.
+ * rhp_walk_args.h -- the argument rules of rhp_walk_responses and
+ * rhp_walk_resume (rhp.h), one statement of them for the kernels' launchers
+ * (rhp_walk.hip) and the host twins (rhp_host.cpp rhp_cpu_walk_responses,
+ * rhp_cpu_walk_resume), with the two clamps all apply to whatever sess_off and
+ * slot_off hold.
  */
 #ifndef RHP_WALK_ARGS_H
 #define RHP_WALK_ARGS_H
@@ -32,6 +33,18 @@ static inline int rhp_walk_check(const rhp_walk_batch_t *w, int device_pointers)
       ((((uintptr_t) w->bytes | (uintptr_t) w->msgs | (uintptr_t) w->slots | (uintptr_t) w->results) & 15u) != 0 ||
        ((uintptr_t) w->hdrs & 7u) != 0))
     return -22;
+  return 0;
+}
+
+/* rhp_walk_resume (rhp.h): rhp_walk_check's answers, and its own two rules
+ * about the states, for its launcher (rhp_walk.hip) and its host twin
+ * (rhp_host.cpp rhp_cpu_walk_resume); a state is two whole 16-byte accesses */
+static inline int rhp_walk_resume_check(const rhp_walk_batch_t *w, const rhp_walk_state_t *states, int device_pointers)
+{
+  const int rc = rhp_walk_check(w, device_pointers);
+  if (rc != 0) return rc;
+  if (!states) return -22;
+  if (device_pointers && ((uintptr_t) states & 15u) != 0) return -22;
   return 0;
 }
 
