@@ -92,6 +92,8 @@ static int all_poison(const void *p, size_t n)
   return 1;
 }
 
+#include "walk_edges_host.h"
+
 /* sess_off and slot_off rows that hold anything, every buffer at its exact size */
 static int garbage(void)
 {
@@ -267,11 +269,12 @@ int main(int argc, char **argv)
       free(buf); free(so); free(sl); free(msgs); free(hdrs); free(slots); free(res);
     }
   }
-  if (garbage() || refusals()) return 1;
+  size_t edge_cases = 0;
+  if (garbage() || refusals() || walk_edges(argc > 2 ? argv[2] : "../../tests/golden/walk_edges.npz", 0, &edge_cases)) return 1;
   free(set_maxh); free(set_flags); free(set_sess); free(set_slot); free(set_byte); free(bytes); free(deframed); free(sess_off);
   free(slot_off); free(n_slots); free(stop); free(consumed); free(written); free(start); free(body_len); free(wire_len); free(result);
   free(body_kind); free(ret); free(status); free(num_headers); free(hdr_lo); free(hdr); free(g_file);
-  printf("walk_responses_host_test OK: %zu sets, %zu sessions, %zu calls, %zu slots compared, %zu bytes moved by the de-framing\n", S, NS,
-         calls, compared, moved);
+  printf("walk_responses_host_test OK: %zu sets, %zu sessions, %zu calls, %zu slots compared, %zu bytes moved by the de-framing, "
+         "%zu cases at the readable end\n", S, NS, calls, compared, moved, edge_cases);
   return 0;
 }

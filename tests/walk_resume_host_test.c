@@ -14,8 +14,10 @@
  * and slot_off [n_sessions + 1], msgs, slots [n_slots_total], hdrs
  * [n_slots_total * max_headers], results and states [n_sessions] -- and the
  * outputs hold 0xC3 first; the sanitizer sees any access outside a buffer.
- * Then states of every kind over sess_off rows that hold anything, and the
- * refusals.  Exits non-zero on the first mismatch.
+ * Then states of every kind over sess_off rows that hold anything, the
+ * refusals, and the rhp_walk_resume cases of tests/golden/walk_edges.npz
+ * (argv[2], or the path from csrc/), each in a block of lim + 16 <= bytes_size bytes
+ * (walk_edges_host.h).  Exits non-zero on the first mismatch.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -94,6 +96,7 @@ static int all_poison(const void *p, size_t n)
   return 1;
 }
 
+#include "walk_edges_host.h"
 
 /* the state the file holds for session-round q, or `in` where it says kept */
 static rhp_walk_state_t state_of(const uint8_t *kept, const uint8_t *phase, const uint8_t *ct, const uint8_t *hex,
@@ -270,8 +273,9 @@ int main(int argc, char **argv)
       free(st); free(in);
     }
   }
-  if (garbage() || refusals()) return 1;
-  printf("walk_resume_host_test OK: %zu sets, %zu rounds run\n", S, rounds_run);
+  size_t edge_cases = 0;
+  if (garbage() || refusals() || walk_edges(argc > 2 ? argv[2] : "../../tests/golden/walk_edges.npz", 1, &edge_cases)) return 1;
+  printf("walk_resume_host_test OK: %zu sets, %zu rounds run, %zu cases at the readable end\n", S, rounds_run, edge_cases);
   free(deframed);
   void *loaded[] = {set_maxh, set_flags, set_nsess, set_round, set_first, states_in, round_q, round_slot, round_byte, bytes, defr_idx, defr_val,
                     len, cap, n_slots, stop, consumed, kept, st_phase, st_ct, st_hex, st_state, st_left, start, body_len, wire_len, result,
