@@ -1009,11 +1009,12 @@ int rhp_frame_messages(const rhp_msg_batch_t *batch, const rhp_frame_args_t *f, 
  * inside the wire span of a completed chunked body -- nothing else.  A message
  * record and a result leave as one 16-byte store, a slot as two, a header
  * record as one 8-byte store.
- * Not here: a header lookup over walked slots (rhp_frame_messages addresses
- * messages by offsets[i], not by slots[i].start); responses to HEAD requests
+ * Not here: responses to HEAD requests
  * (their framing headers describe a body that is not sent); resuming a partial
  * chunked body across rounds (rhp_walk_resume, below, carries the walk from
- * round to round).
+ * round to round).  The header lookup over the walked slots is
+ * rhp_lookup_walked, below (rhp_frame_messages addresses messages by
+ * offsets[i], not by slots[i].start).
  * -EINVAL (rhp_walk_args.h): a NULL w; max_headers above RHP_MAX_HEADERS; a
  * flag bit that is not named here; n_slots_total * max_headers >= 2^32;
  * RHP_WALK_DEFRAME with a bytes_rw that is NULL or not `bytes`; with
@@ -1153,6 +1154,71 @@ typedef struct rhp_walk_state {   /* 32 B, two 16-byte accesses; all zero before
 } rhp_walk_state_t;
 
 int rhp_walk_resume(const rhp_walk_batch_t *w, rhp_walk_state_t *states /* device [n_sessions], 16-byte aligned */, void *stream);
+
+/*
+ * The header lookup over the slots of a walk: http_field_lookup
+ * (src/reactor/http.c:167-175) for up to 16 names over the rhp_msg_t /
+ * rhp_hdr_t records rhp_walk_responses or rhp_walk_resume left on the device,
+ * the response side's rhp_classify_sessions.  w is the batch exactly as the
+ * walk left it on `stream`; RHP_WALK_DEFRAME may be set or clear (a head never
+ * moves: the de-framing writes only inside the wire span of a chunked body).
+ * For every slot i < n_slots_total and every name j, fields[j * n_slots_total
+ * + i] is written.
+ *   Owner.  s is the last session with slot_off[s] <= i, s < n_sessions (a
+ *   bisection per slot).
+ *   In use.  With lo = slot_off[s], hi = slot_off[s+1]: lo <= i < hi, hi <=
+ *   n_slots_total and i - lo < results[s].n_slots.  This one test is what lets
+ *   any load of slots[i], msgs[i] or hdrs[i * max_headers + k] through,
+ *   whatever the search returned: a slot the walk did not write holds stale
+ *   records or nothing and is never read.
+ *   Head.  An in-use slot is a head when slots[i].result == 1 and msgs[i].ret
+ *   > 0.  (A continuation slot of rhp_walk_resume has ret == 0, a slot that
+ *   stopped with RHP_WALK_HEAD or RHP_WALK_BAD has result != 1,
+ *   RHP_RET_TOOLONG is negative.)
+ *   Inside.  With st = slots[i].start and ret = msgs[i].ret, a head is looked
+ *   up only when sess_off[s] <= st <= sess_off[s+1], ret <= sess_off[s+1] - st
+ *   and st + ret <= bytes_size rounded down to a multiple of 4 (names are read
+ *   as the aligned dwords that hold them, as rhp_frame_messages reads them).
+ *   Every head the walk wrote passes; a crafted record that does not is absent.
+ *   Lookup.  rhp_frame_messages' lookup for its caller's names: of the records
+ *   k < min(num_headers, max_headers), request-major, those with name_off ==
+ *   RHP_NAME_NULL (an obs-fold line) are skipped, and the first counts whose
+ *   name has name j's length and equals it with a..z mapped to A..Z on both
+ *   sides, no other byte.  fields[j * n_slots_total + i] = {value_off,
+ *   value_len}, an offset from st; a present header with an empty value gives
+ *   {value_off, 0}.  A record whose name does not lie inside [0, ret) matches
+ *   nothing (no parsed record is like that).
+ *   Absent.  Every other slot gets {RHP_NAME_NULL, 0} for every name: a slot
+ *   not in use, a continuation slot, a slot that stopped with HEAD or BAD, a
+ *   head that is not inside, a missing header, any slot when max_headers == 0.
+ * Memory.  Nothing is read outside bytes[0, bytes_size), sess_off[0,
+ * n_sessions], slot_off[0, n_sessions], results[0, n_sessions) and the records
+ * of the slots in use, whatever slot_off, sess_off, results or the records
+ * hold; records k >= num_headers are never read, name bytes only of records
+ * whose name_len is a name's.  Nothing is written outside fields[0, n_names *
+ * n_slots_total).  With slot_off not monotone a slot may be reported absent;
+ * the answers are otherwise unspecified.
+ * -EINVAL (rhp_lookup_args.h): whatever rhp_walk_responses refuses about w; a
+ * NULL l; reserved != 0; n_names == 0 or above RHP_CLASSIFY_MAX_NAMES; an empty
+ * name or one longer than RHP_CLASSIFY_NAME_MAX; a NULL text, names or fields;
+ * a NULL results with n_sessions > 0; fields not 4-byte aligned (device
+ * pointers only).  n_slots_total == 0 or n_sessions == 0 succeeds and launches
+ * nothing: with no session there is none to own a slot, so with n_sessions ==
+ * 0 and slots present nothing is launched either and fields is not touched.
+ * Launch contract as rhp_classify_sessions: one launch, one slot per lane,
+ * asynchronous on `stream`, no allocation, no copy, no synchronisation; the
+ * names travel in the kernel argument and the caller's tables are free when
+ * the call returns; thread-safe.
+ */
+typedef struct rhp_walk_lookup {
+  const uint8_t    *text;      /* host: the bytes of the names (as rhp_classify_t) */
+  const rhp_span_t *names;     /* host [n_names]: spans of `text` */
+  uint32_t          n_names;   /* 1 .. RHP_CLASSIFY_MAX_NAMES */
+  uint32_t          reserved;  /* must be 0 */
+  rhp_fieldref_t   *fields;    /* device [n_names * n_slots_total], name-major: fields[j * n_slots_total + i] */
+} rhp_walk_lookup_t;
+
+int rhp_lookup_walked(const rhp_walk_batch_t *w, const rhp_walk_lookup_t *l, void *stream);
 
 
 #ifdef __cplusplus

@@ -161,6 +161,14 @@ int rhp_cpu_walk_responses(const rhp_walk_batch_t *w);
  * Sequential; a caller with threads hands each a range of sessions. */
 int rhp_cpu_walk_resume(const rhp_walk_batch_t *w, rhp_walk_state_t *states);
 
+/* rhp_lookup_walked (rhp.h) over a walk's records in host memory, as
+ * rhp_cpu_walk_responses or rhp_cpu_walk_resume left them: every pointer of `w`
+ * and of `l` is host memory, of any alignment, and there is no stream.  The
+ * same fields and the same -22 (rhp_lookup_args.h; the alignment rules are the
+ * device's alone).  Of the bytes only names inside a looked-up head are read,
+ * and no record of a slot that is not in use.  Sequential. */
+int rhp_cpu_lookup_walked(const rhp_walk_batch_t *w, const rhp_walk_lookup_t *l);
+
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */
 typedef struct rhp_phr_header {
   const char *name;

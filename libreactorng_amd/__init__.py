@@ -67,7 +67,7 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
                "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
                "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages", "rhp_decode_chunked", "rhp_frame_messages",
-               "rhp_walk_responses", "rhp_walk_resume")
+               "rhp_walk_responses", "rhp_walk_resume", "rhp_lookup_walked")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
@@ -75,7 +75,8 @@ HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_spl
                 "rhp_test_chunk_exact", "rhp_cpu_classify_sessions", "rhp_cpu_reply_sessions", "rhp_cpu_gather_wide",
                 "rhp_cpu_split_sessions", "rhp_cpu_parse_messages", "rhp_phr_parse_response", "rhp_phr_parse_headers",
                 "rhp_cpu_decode_chunked", "rhp_phr_decode_chunked", "rhp_phr_decode_chunked_is_in_data",
-                "rhp_cpu_frame_messages", "rhp_cpu_walk_responses", "rhp_cpu_walk_resume")
+                "rhp_cpu_frame_messages", "rhp_cpu_walk_responses", "rhp_cpu_walk_resume",
+                "rhp_cpu_lookup_walked")
 
 _rhp = None
 _host = None
@@ -226,6 +227,15 @@ WALK_STATE_DTYPE = np.dtype([("decoder", CHUNKED_DTYPE), ("left", "<u8"), ("phas
 assert WALK_STATE_DTYPE.itemsize == 32
 
 
+class WalkLookup(ctypes.Structure):
+    """rhp_walk_lookup_t (include/rhp.h): the lookup names and the output of rhp_lookup_walked"""
+    _fields_ = [("text", ctypes.c_void_p), ("names", ctypes.c_void_p), ("n_names", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("fields", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(WalkLookup) == 32
+
+
 def _torch_hip_runtime() -> str | None:
     """Path of the HIP runtime torch ships (torch/lib/libamdhip64.so), found
     without importing torch."""
@@ -314,6 +324,8 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_walk_responses.restype = ctypes.c_int
         _rhp.rhp_walk_resume.argtypes = [ctypes.POINTER(WalkBatch), vp, vp]
         _rhp.rhp_walk_resume.restype = ctypes.c_int
+        _rhp.rhp_lookup_walked.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkLookup), vp]
+        _rhp.rhp_lookup_walked.restype = ctypes.c_int
     return _rhp
 
 
@@ -388,6 +400,8 @@ def host() -> ctypes.CDLL:
         _host.rhp_cpu_walk_responses.restype = ctypes.c_int
         _host.rhp_cpu_walk_resume.argtypes = [ctypes.POINTER(WalkBatch), vp]
         _host.rhp_cpu_walk_resume.restype = ctypes.c_int
+        _host.rhp_cpu_lookup_walked.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkLookup)]
+        _host.rhp_cpu_lookup_walked.restype = ctypes.c_int
     return _host
 
 
@@ -2220,3 +2234,105 @@ def walk_resume_gpu(buf, sess_off, slot_off, states=None, max_headers: int = 16,
             g.check()
     return _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
                         db.view.cpu().numpy(), ns, nt, max_headers) + (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE), gt)
+
+
+# The header lookup over the slots of a walk (rhp.h rhp_lookup_walked): the records stay where the walk left
+# them, and only `fields` goes back to the host.
+
+LOOKUP_POISON = 0xC3   # what fields holds before a call (tests): no answer's value
+
+
+def _lookup_fields(fields, n_names, n_slots):
+    """fields FIELDREF_DTYPE [n_names, n_slots] from the output's bytes"""
+    return fields[: 4 * n_names * n_slots].view(FIELDREF_DTYPE).reshape(n_names, n_slots)
+
+
+def lookup_walked_cpu(records, buf, sess_off, slot_off, names, max_headers: int = 16, flags: int = 0,
+                      bytes_size: int | None = None, n_slots_total: int | None = None):
+    """rhp_cpu_lookup_walked (include/rhp_host.h) over `records`: (results, slots, msgs, hdrs) as
+    walk_responses_cpu or walk_resume_cpu returned them (their first four), or crafted ones; buf, sess_off and
+    slot_off as that walk got them (buf may be the bytes it left).  Returns fields FIELDREF_DTYPE [n_names,
+    n_slots_total]; it held LOOKUP_POISON before the call."""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    ns = len(sess_off) - 1
+    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    res, slots, msgs, hdrs = (np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in records[:4])
+    text, nm, _ = classify_tables(names)
+    fields = np.full(max(4 * len(nm) * nt, 1), LOOKUP_POISON, dtype=np.uint8)
+    w = WalkBatch(_ptr(buf), _ptr(buf), buf.size if bytes_size is None else bytes_size, _ptr(sess_off), _ptr(slot_off), ns,
+                  nt, max_headers, flags, _ptr(msgs) if msgs.size else None, _ptr(hdrs) if hdrs.size else None,
+                  _ptr(slots) if slots.size else None, _ptr(res) if res.size else None)
+    l = WalkLookup(_ptr(text), _ptr(nm), len(nm), 0, _ptr(fields))
+    rc = host().rhp_cpu_lookup_walked(ctypes.byref(w), ctypes.byref(l))
+    if rc != 0:
+        raise RuntimeError(f"rhp_cpu_lookup_walked failed: {rc}")
+    return _lookup_fields(fields, len(nm), nt)
+
+
+def lookup_walked_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sessions: int, n_slots_total: int,
+                         max_headers: int, flags: int, msgs_t, hdrs_t, slots_t, results_t, names, fields_t, stream=None):
+    """One rhp_lookup_walked call over device tensors on the stream (default: the current one): the batch as
+    walk_responses_device or walk_resume_device left it; fields_t u8 (4 * len(names) * n_slots_total bytes).
+    Nothing is synchronised or copied: the tensors are the call's only inputs and outputs (the names travel in
+    the launch)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    text, nm, _ = classify_tables(names)
+    w = WalkBatch(_addr(bytes_t), _addr(bytes_t), bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions,
+                  n_slots_total, max_headers, flags, _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+    l = WalkLookup(_ptr(text), _ptr(nm), len(nm), 0, _addr(fields_t))
+    rc = lib().rhp_lookup_walked(ctypes.byref(w), ctypes.byref(l), ctypes.c_void_p(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_lookup_walked failed: {rc}")
+
+
+def lookup_walked_gpu(buf, sess_off, slot_off, names, max_headers: int = 16, flags: int = 0, guard: int = 0,
+                      fill: int = LOOKUP_POISON, records=None, states=None, resume: bool = False,
+                      bytes_size: int | None = None, n_slots_total: int | None = None):
+    """The sessions walked (rhp_walk_responses; with resume or states: one round of rhp_walk_resume, states as
+    walk_resume_gpu takes them) and looked up (rhp_lookup_walked) on the GPU, on one stream, the walk's records
+    left on the device between the two.  bytes, msgs, hdrs, slots, results, states and fields are Guarded device
+    buffers (guard bytes on both sides, checked after the call); the records and fields hold `fill` first.
+    records: (results, slots, msgs, hdrs) copied in instead of walking (tests: crafted records; their own bytes
+    in front, `fill` behind them).  Returns (fields as lookup_walked_cpu, what walk_responses_gpu or
+    walk_resume_gpu returns)."""
+    import torch
+    buf = np.array(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    ns, nn = len(sess_off) - 1, len(names)
+    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    resume = resume or states is not None
+    size = buf.size if bytes_size is None else bytes_size
+    db = Guarded("bytes", buf.size, guard, data=buf)
+    gm = Guarded("msgs", max(16 * nt, 1), guard, fill=fill)
+    gh = Guarded("hdrs", max(8 * nt * max_headers, 1), guard, fill=fill)
+    gs = Guarded("slots", max(32 * nt, 1), guard, fill=fill)
+    gr = Guarded("results", max(16 * ns, 1), guard, fill=fill)
+    gf = Guarded("fields", max(4 * nn * nt, 1), guard, fill=fill)
+    gt = None
+    if resume and records is None:
+        gt = states if isinstance(states, Guarded) else Guarded("states", max(32 * ns, 1), guard, data=_walk_states(states, ns))
+    dso = torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda")
+    dsl = torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda")
+    if records is not None:
+        for g, a in zip((gr, gs, gm, gh), records[:4]):
+            a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            if a.size:
+                g.view[: a.size].copy_(torch.from_numpy(a.copy()))
+    elif resume:
+        walk_resume_device(db.view, size, dso, dsl, ns, nt, max_headers, flags, gm.view, gh.view, gs.view, gr.view, gt.view)
+    else:
+        walk_responses_device(db.view, size, dso, dsl, ns, nt, max_headers, flags, gm.view, gh.view, gs.view, gr.view)
+    lookup_walked_device(db.view, size, dso, dsl, ns, nt, max_headers, flags, gm.view, gh.view, gs.view, gr.view, names, gf.view)
+    torch.cuda.synchronize()
+    if guard:
+        for g in (db, gm, gh, gs, gr, gf) + ((gt,) if gt is not None else ()):
+            g.check()
+    out = _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
+                       db.view.cpu().numpy(), ns, nt, max_headers)
+    if gt is not None:
+        out += (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE), gt)
+    return _lookup_fields(gf.view.cpu().numpy(), nn, nt), out

@@ -32,6 +32,11 @@
  * records rhp_parse_messages leaves, with the framing of http.c:204-233 decided
  * in the same walk: its kernel stands here because it shares fold4, same_text,
  * CTables and pack_tables.
+ *
+ * rhp_lookup_walked (rhp.h) is rhp_classify_sessions' lookup over the slots a
+ * response walk (rhp_walk.hip) left: one slot per lane, the slot's session by
+ * binary search over slot_off[], the head's first byte from slots[i].start,
+ * the rules that let a slot through in rhp_lookup_args.h.
  */
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -42,6 +47,7 @@
 #include "rhp_classify_args.h"
 #include "rhp_device.h"
 #include "rhp_frame_args.h"
+#include "rhp_lookup_args.h"
 #include "rhp_scalar.h"
 
 namespace {
@@ -593,6 +599,101 @@ __global__ __launch_bounds__(256) void rhp_frame_messages_kernel(FParams p)
   if (p.decoders && kind == RHP_FRAME_CHUNKED) p.decoders[i] = uint4{0u, 0u, p.consume_trailer, 0u};
 }
 
+/* ---- rhp_lookup_walked ---- */
+
+struct WParams {
+  CTables         t;          /* first, as CParams */
+  const uint8_t  *bytes;
+  const uint64_t *sess_off, *slot_off;
+  uint64_t        readable;   /* rhp_lookup_readable */
+  const uint4    *msgs;
+  const uint2    *hdrs;
+  const uint4    *slots;      /* two per slot */
+  const uint4    *results;
+  uint32_t       *fields;
+  uint32_t        n, m, n_names, n_sessions;
+};
+static_assert(offsetof(WParams, t) == 0, "the tables lead the argument");
+static_assert(sizeof(WParams) <= 4096, "a kernel argument holds 4 KiB");
+static_assert(sizeof(rhp_walk_slot_t) == 32 && offsetof(rhp_walk_slot_t, start) == 0 && offsetof(rhp_walk_slot_t, result) == 24 &&
+              sizeof(rhp_walk_result_t) == 16 && offsetof(rhp_walk_result_t, n_slots) == 0, "records as 16-byte accesses");
+
+/* One slot of the walk per lane, rhp_classify_sessions_kernel's mapping over
+ * the records rhp_walk_responses / rhp_walk_resume left: the lane finds the
+ * last session whose slot_off is at or below its slot and tests that the slot
+ * is one that session's walk wrote (rhp_lookup_args.h: the test that lets a
+ * load through, whatever the search returned); only then it loads msgs[i] as
+ * one 16-byte load and the slot's start and result from its two halves, and,
+ * for a head that lies inside its session's bytes, walks the rhp_hdr_t records
+ * k < num_headers (request-major, 8-byte loads) -- name_len against the length
+ * mask, the name's bytes only on a length match -- until every name is found.
+ * A slot the walk did not write holds stale records or nothing and is never
+ * read. */
+__global__ __launch_bounds__(256) void rhp_lookup_walked_kernel(WParams p)
+{
+  __shared__ uint32_t tab[kTabDwords];
+  __shared__ uint16_t lenmask[RHP_CLASSIFY_NAME_MAX + 1u];
+  {
+#if defined(__HIP_DEVICE_COMPILE__)   /* (as rhp_classify_kernel) */
+    const ka32 *ka = (const ka32 *) __builtin_amdgcn_kernarg_segment_ptr();
+#else
+    const ka32 *ka = nullptr;
+#endif
+    for (uint32_t t = threadIdx.x; t < kTabDwords; t += blockDim.x) tab[t] = ka[t];
+    if (threadIdx.x <= RHP_CLASSIFY_NAME_MAX) {
+      const ka32 *nl = ka + offsetof(CTables, name_len) / 4u;
+      uint32_t mk = 0;
+      for (uint32_t j = 0; j < p.n_names; j++) mk |= (((nl[j >> 2] >> (8u * (j & 3u))) & 0xffu) == threadIdx.x ? 1u : 0u) << j;
+      lenmask[threadIdx.x] = (uint16_t) mk;
+    }
+  }
+  __syncthreads();
+  const uint32_t *names = tab + offsetof(CTables, name) / 4u;
+
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = p.n, m = p.m;
+  if (i >= n) return;
+
+  /* ---- the slot's session: the sessions before `above` have slot_off <= i ---- */
+  const uint32_t above = rhp_lookup_sessions_upto(p.slot_off, p.n_sessions, i);
+
+  /* ---- in use?  a head?  inside its session?  then its first byte and its records ---- */
+  int32_t ret = 0;
+  uint32_t nh = 0;
+  uint64_t at0 = 0;
+  if (above) {
+    const uint32_t s = above - 1u;
+    const uint64_t lo = p.slot_off[s], hi = p.slot_off[s + 1u];
+    const uint32_t n_slots = p.results[s].x;
+    if (rhp_lookup_in_use(i, lo, hi, n_slots, n)) {
+      const uint4 q = p.msgs[i], s0 = p.slots[2u * (uint64_t) i], s1 = p.slots[2u * (uint64_t) i + 1u];
+      const uint64_t st = (uint64_t) s0.x | (uint64_t) s0.y << 32;
+      if (rhp_lookup_is_head((int32_t) s1.z, (int32_t) q.x) &&
+          rhp_lookup_inside(st, (int32_t) q.x, p.sess_off[s], p.sess_off[s + 1u], p.readable)) {
+        ret = (int32_t) q.x;
+        at0 = st;
+        nh = q.w & 0xffffu;
+      }
+    }
+  }
+  if (nh > m) nh = m;   /* never more records than the batch holds */
+
+  /* ---- header lookup over rhp_hdr_t records ---- */
+  const uint32_t all = (1u << p.n_names) - 1u;
+  uint32_t found = 0;
+  for (uint32_t k = 0; k < nh && found != all; k++) {
+    const uint2 h = p.hdrs[(uint64_t) i * m + k];
+    const uint32_t noff = h.x & 0xffffu, nl = h.x >> 16;
+    if (noff == RHP_NAME_NULL) continue;   /* name == NULL: an obs-fold line */
+    uint32_t cand = nl <= RHP_CLASSIFY_NAME_MAX ? (uint32_t) lenmask[nl] & ~found : 0u;
+    if (cand == 0) continue;
+    if (noff + nl > (uint32_t) ret) continue;   /* (a parsed name lies inside its header section) */
+    cand = same_text<true>(p.bytes + at0 + noff, nl, cand, names, [](uint32_t j) { return j * kNameDwords; });
+    for (uint32_t c = cand; c; c &= c - 1u) p.fields[(uint64_t) __builtin_ctz(c) * n + i] = h.y;
+    found |= cand;
+  }
+  for (uint32_t c = all & ~found; c; c &= c - 1u) p.fields[(uint64_t) __builtin_ctz(c) * n + i] = RHP_NAME_NULL;
+}
+
 }  // namespace
 
 extern "C" int rhp_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c, void *stream)
@@ -650,6 +751,31 @@ extern "C" int rhp_frame_messages(const rhp_msg_batch_t *b, const rhp_frame_args
   p.s_req = hmajor ? 1u : b->max_headers;
   p.s_hdr = hmajor ? b->n : 1u;
   hipLaunchKernelGGL(rhp_frame_messages_kernel, dim3((uint32_t) (((uint64_t) b->n + 255u) / 256u)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), p);
+  return (int) hipGetLastError();
+}
+
+extern "C" int rhp_lookup_walked(const rhp_walk_batch_t *w, const rhp_walk_lookup_t *l, void *stream)
+{
+  const int rc = rhp_lookup_walked_check(w, l, 1);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  WParams p;
+  const rhp_classify_t names = {l->text, l->names, nullptr, l->n_names, 0, nullptr, nullptr};
+  pack_tables(&names, p.t);
+  p.bytes = w->bytes;
+  p.sess_off = w->sess_off;
+  p.slot_off = w->slot_off;
+  p.readable = rhp_lookup_readable(w->bytes_size);
+  p.msgs = reinterpret_cast<const uint4 *>(w->msgs);
+  p.hdrs = reinterpret_cast<const uint2 *>(w->hdrs);
+  p.slots = reinterpret_cast<const uint4 *>(w->slots);
+  p.results = reinterpret_cast<const uint4 *>(w->results);
+  p.fields = reinterpret_cast<uint32_t *>(l->fields);
+  p.n = w->n_slots_total;
+  p.m = w->max_headers;
+  p.n_names = l->n_names;
+  p.n_sessions = w->n_sessions;
+  hipLaunchKernelGGL(rhp_lookup_walked_kernel, dim3((uint32_t) (((uint64_t) w->n_slots_total + 255u) / 256u)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), p);
   return (int) hipGetLastError();
 }

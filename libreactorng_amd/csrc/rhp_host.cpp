@@ -23,6 +23,7 @@
 #include "rhp_chunked_args.h"
 #include "rhp_frame_args.h"
 #include "rhp_walk_args.h"
+#include "rhp_lookup_args.h"
 #include "rhp_host_exact.h"
 
 using namespace rhp;
@@ -606,6 +607,35 @@ extern "C" int rhp_cpu_walk_resume(const rhp_walk_batch_t *w, rhp_walk_state_t *
     rhp_walk_result_t r;
     if (walk_resume_t(io, a, e, (uint32_t) lo, (uint32_t) hi, w->max_headers, w->flags, &st, &r)) memcpy(&states[s], &st, sizeof st);
     w->results[s] = r;
+  }
+  return 0;
+}
+
+/* rhp_lookup_walked (rhp.h) on the host, every pointer in host memory: slot by
+ * slot the kernel's own rules (rhp_lookup_args.h: the owner by the same
+ * bisection, in use, head, inside) and then classify_one, the lookup every
+ * classify twin and rhp_cpu_frame_messages run, from slots[i].start.  Every
+ * slot is absent first.  It shares the argument check with the launcher. */
+extern "C" int rhp_cpu_lookup_walked(const rhp_walk_batch_t *w, const rhp_walk_lookup_t *l)
+{
+  const int rc = rhp_lookup_walked_check(w, l, 0);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const uint32_t n = w->n_slots_total, m = w->max_headers;
+  const uint64_t readable = rhp_lookup_readable(w->bytes_size);
+  const rhp_classify_t c = {l->text, l->names, nullptr, l->n_names, 0, l->fields, nullptr};
+  for (uint32_t i = 0; i < n; i++) {
+    classify_absent(&c, n, i);
+    const uint32_t above = rhp_lookup_sessions_upto(w->slot_off, w->n_sessions, i);
+    if (!above) continue;
+    const uint32_t s = above - 1u;
+    if (!rhp_lookup_in_use(i, w->slot_off[s], w->slot_off[s + 1], w->results[s].n_slots, n)) continue;
+    const int32_t ret = w->msgs[i].ret;
+    const uint64_t st = w->slots[i].start;
+    if (!rhp_lookup_is_head(w->slots[i].result, ret) || !rhp_lookup_inside(st, ret, w->sess_off[s], w->sess_off[s + 1], readable)) continue;
+    rhp_req_t r = {};
+    r.ret = ret;
+    r.num_headers = w->msgs[i].num_headers;
+    classify_one(&c, n, m, i, w->bytes + st, r, [&](uint32_t k) -> const rhp_hdr_t & { return w->hdrs[(size_t) i * m + k]; });
   }
   return 0;
 }
