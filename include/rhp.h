@@ -1009,8 +1009,9 @@ int rhp_frame_messages(const rhp_msg_batch_t *batch, const rhp_frame_args_t *f, 
  * inside the wire span of a completed chunked body -- nothing else.  A message
  * record and a result leave as one 16-byte store, a slot as two, a header
  * record as one 8-byte store.
- * Not here: responses to HEAD requests
- * (their framing headers describe a body that is not sent); resuming a partial
+ * Not here: responses to HEAD requests (their framing headers describe a body
+ * that is not sent; the answer is in the request, and rhp_walk_answers, below,
+ * is this walk told which requests were HEAD); resuming a partial
  * chunked body across rounds (rhp_walk_resume, below, carries the walk from
  * round to round).  The header lookup over the walked slots is
  * rhp_lookup_walked, below (rhp_frame_messages addresses messages by
@@ -1154,6 +1155,80 @@ typedef struct rhp_walk_state {   /* 32 B, two 16-byte accesses; all zero before
 } rhp_walk_state_t;
 
 int rhp_walk_resume(const rhp_walk_batch_t *w, rhp_walk_state_t *states /* device [n_sessions], 16-byte aligned */, void *stream);
+
+/*
+ * The two walks above told what was asked.  A reply to a HEAD request carries
+ * the framing headers of the GET's reply and no body; which reply that is
+ * stands in the request, not in the response, and a proxy knows which of its
+ * outstanding requests were HEAD.  The same queue says which request a slot
+ * answers: the count of slots is not the count of answered requests, since an
+ * interim response takes a slot and answers nothing and a continuation slot is
+ * no response at all.  With states == NULL the call is rhp_walk_responses with
+ * the rules below added, with states it is rhp_walk_resume with them added; the
+ * batch, the flags, the clamps, the stop codes, the state and the memory
+ * contract are theirs, word for word.
+ *   Queue.  Session s's outstanding requests, oldest first, are q in
+ *   [req_off[s], req_off[s+1]): nq = req_off[s+1] - req_off[s].  A pair that is
+ *   not ordered or reaches beyond n_req_total owns no request: nq = 0.  k = 0
+ *   at the start of every round: the caller pops answered[s] requests after
+ *   each round, so a round's queue starts at the first unanswered request
+ *   (which is why rhp_walk_state_t carries no count).
+ *   Interim.  A head -- a slot with msgs[slot].ret > 0 and result 1 -- whose
+ *   status is 100..199 is interim: it has no body already (the rule above) and
+ *   does not advance k.  101 counts as interim: a protocol switch, like a 2xx
+ *   to CONNECT, makes the connection something other than HTTP, and neither is
+ *   handled here.
+ *   Final.  Every other head with result 1 answers request k.  If k < nq and
+ *   bit req_off[s] + k of head_bits is set the request was a HEAD: body_kind
+ *   stays what the framing said, body_len = wire_len = 0, and the walk goes on
+ *   behind the head -- the shape of the 1xx/204/304 rule.  No byte is moved,
+ *   also with RHP_WALK_DEFRAME; no stop of BODY or CLOSE follows and no state
+ *   is armed, also when Content-Length exceeds what is there or when neither
+ *   header is present without RHP_WALK_NONE_EMPTY.  A framing answer of -1 (a
+ *   bad Content-Length) is still RHP_WALK_BAD.  A HEAD bit on a 204 or 304
+ *   reply changes nothing.  After the slot, k++.  Requests at k >= nq count as
+ *   not HEAD; nothing is read for them.
+ *   THE REFERENCE HAS NO RULE HERE, and no response walker: this is the walk's
+ *   second invented rule (RFC 9112 section 6.3 item 1), beside the
+ *   1xx/204/304 one.
+ *   Outputs.  answered[s] = k at exit, for every session; 0 on the paths that
+ *   keep the state as it lies (a corrupt or dead state, an empty round, a
+ *   continuation with no slot).  It may exceed nq when responses arrive that
+ *   nobody asked for: that is the caller's finding.  With slot_req != NULL
+ *   every written slot gets its entry and no other slot does: a head with
+ *   result 1 gets k as it was before the slot advanced it (an interim head
+ *   names the request it precedes); a continuation slot and a slot that
+ *   stopped with HEAD or BAD get RHP_WALK_REQ_NONE.
+ *   Equivalence.  With every bit clear, or every nq == 0, the call leaves byte
+ *   for byte what rhp_walk_responses / rhp_walk_resume leave in msgs, hdrs,
+ *   slots, results, states and bytes.
+ * Memory as the walk's; in addition req_off[0, n_sessions] is read, and of
+ * head_bits words below (n_req_total + 31) / 32, a word only when some k < nq
+ * of the session falls into it (one 4-byte load per 32 requests of a session's
+ * queue); answered[0, n_sessions) is written, and the slot_req entries of the
+ * written slots, as plain 4-byte stores.
+ * -EINVAL (rhp_walk_args.h): whatever the underlying walk refuses; a NULL x;
+ * reserved != 0; with n_sessions > 0 a NULL req_off or answered; a NULL
+ * head_bits with n_req_total > 0; req_off, head_bits, answered or slot_req not
+ * 4-byte aligned (device pointers only).  n_sessions == 0 succeeds and
+ * launches nothing.
+ * Launch contract as rhp_walk_responses: one launch, one session per lane,
+ * asynchronous on `stream`, no allocation, no copy, no synchronisation.
+ */
+#define RHP_WALK_REQ_NONE 0xFFFFFFFFu   /* slot_req: the slot answers no request */
+
+typedef struct rhp_walk_asked {
+  const uint32_t *req_off;     /* device [n_sessions + 1]: session s's outstanding requests, oldest first,
+                                  are q in [req_off[s], req_off[s+1]) */
+  const uint32_t *head_bits;   /* device [(n_req_total + 31) / 32]: bit (q & 31) of word q >> 5 set: request q was a HEAD */
+  uint32_t        n_req_total; /* host copy of req_off[n_sessions] */
+  uint32_t        reserved;    /* must be 0 */
+  uint32_t       *answered;    /* device [n_sessions] */
+  uint32_t       *slot_req;    /* device [n_slots_total], or NULL */
+} rhp_walk_asked_t;
+
+int rhp_walk_answers(const rhp_walk_batch_t *w, rhp_walk_state_t *states /* or NULL */, const rhp_walk_asked_t *x,
+                     void *stream);
 
 /*
  * The header lookup over the slots of a walk: http_field_lookup

@@ -161,6 +161,15 @@ int rhp_cpu_walk_responses(const rhp_walk_batch_t *w);
  * Sequential; a caller with threads hands each a range of sessions. */
 int rhp_cpu_walk_resume(const rhp_walk_batch_t *w, rhp_walk_state_t *states);
 
+/* rhp_walk_answers (rhp.h) over sessions, states (or NULL) and a queue in host
+ * memory: every pointer of `w` and `x` is a host pointer, the four arrays of
+ * `x` uint32_t arrays as the language aligns them.  The statement is the
+ * kernels' (rhp_scalar.h walk_session_t / walk_resume_t with the Asked policy),
+ * session by session, with the same argument check, the same clamps and the
+ * same -22 (rhp_walk_args.h; the alignment rules are the device's alone).
+ * Returns 0. */
+int rhp_cpu_walk_answers(const rhp_walk_batch_t *w, rhp_walk_state_t *states /* or NULL */, const rhp_walk_asked_t *x);
+
 /* rhp_lookup_walked (rhp.h) over a walk's records in host memory, as
  * rhp_cpu_walk_responses or rhp_cpu_walk_resume left them: every pointer of `w`
  * and of `l` is host memory, of any alignment, and there is no stream.  The

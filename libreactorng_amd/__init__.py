@@ -67,7 +67,7 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
                "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
                "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages", "rhp_decode_chunked", "rhp_frame_messages",
-               "rhp_walk_responses", "rhp_walk_resume", "rhp_lookup_walked")
+               "rhp_walk_responses", "rhp_walk_resume", "rhp_lookup_walked", "rhp_walk_answers")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
@@ -76,7 +76,7 @@ HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_spl
                 "rhp_cpu_split_sessions", "rhp_cpu_parse_messages", "rhp_phr_parse_response", "rhp_phr_parse_headers",
                 "rhp_cpu_decode_chunked", "rhp_phr_decode_chunked", "rhp_phr_decode_chunked_is_in_data",
                 "rhp_cpu_frame_messages", "rhp_cpu_walk_responses", "rhp_cpu_walk_resume",
-                "rhp_cpu_lookup_walked")
+                "rhp_cpu_lookup_walked", "rhp_cpu_walk_answers")
 
 _rhp = None
 _host = None
@@ -236,6 +236,16 @@ class WalkLookup(ctypes.Structure):
 assert ctypes.sizeof(WalkLookup) == 32
 
 
+class WalkAsked(ctypes.Structure):
+    """rhp_walk_asked_t (include/rhp.h): the sessions' queues of outstanding requests and the outputs of rhp_walk_answers"""
+    _fields_ = [("req_off", ctypes.c_void_p), ("head_bits", ctypes.c_void_p), ("n_req_total", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("answered", ctypes.c_void_p), ("slot_req", ctypes.c_void_p)]
+
+
+WALK_REQ_NONE = 0xFFFFFFFF   # RHP_WALK_REQ_NONE
+assert ctypes.sizeof(WalkAsked) == 40
+
+
 def _torch_hip_runtime() -> str | None:
     """Path of the HIP runtime torch ships (torch/lib/libamdhip64.so), found
     without importing torch."""
@@ -326,6 +336,8 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_walk_resume.restype = ctypes.c_int
         _rhp.rhp_lookup_walked.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkLookup), vp]
         _rhp.rhp_lookup_walked.restype = ctypes.c_int
+        _rhp.rhp_walk_answers.argtypes = [ctypes.POINTER(WalkBatch), vp, ctypes.POINTER(WalkAsked), vp]
+        _rhp.rhp_walk_answers.restype = ctypes.c_int
     return _rhp
 
 
@@ -402,6 +414,8 @@ def host() -> ctypes.CDLL:
         _host.rhp_cpu_walk_resume.restype = ctypes.c_int
         _host.rhp_cpu_lookup_walked.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkLookup)]
         _host.rhp_cpu_lookup_walked.restype = ctypes.c_int
+        _host.rhp_cpu_walk_answers.argtypes = [ctypes.POINTER(WalkBatch), vp, ctypes.POINTER(WalkAsked)]
+        _host.rhp_cpu_walk_answers.restype = ctypes.c_int
     return _host
 
 
@@ -2234,6 +2248,125 @@ def walk_resume_gpu(buf, sess_off, slot_off, states=None, max_headers: int = 16,
             g.check()
     return _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
                         db.view.cpu().numpy(), ns, nt, max_headers) + (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE), gt)
+
+
+# The walk told which requests were HEAD (rhp.h rhp_walk_answers): req_off (u32 [n_sessions + 1]) cuts the
+# sessions' queues of outstanding requests out of head_bits (u32 words, bit q: request q was a HEAD); `answered`
+# (u32 [n_sessions]) and `slot_req` (u32 [n_slots_total]) come back behind the walk's own outputs.
+
+
+def head_bits_of(heads) -> np.ndarray:
+    """head_bits (u32 [(n + 31) // 32], at least one word) from one truth value per request"""
+    heads = np.asarray(heads, dtype=bool)
+    words = np.zeros(max((heads.size + 31) // 32, 1), dtype=np.uint32)
+    for q in np.flatnonzero(heads):
+        words[q >> 5] |= np.uint32(1 << (int(q) & 31))
+    return words
+
+
+def _walk_asked(req_off, head_bits, n_req_total):
+    """(req_off u32, head_bits u32 with at least one word, n_req_total) as the call takes them"""
+    req_off = np.ascontiguousarray(req_off, dtype=np.uint32)
+    head_bits = np.ascontiguousarray(head_bits, dtype=np.uint32).reshape(-1)
+    if head_bits.size == 0:
+        head_bits = np.zeros(1, dtype=np.uint32)
+    return req_off, head_bits, int(req_off[-1]) if n_req_total is None else n_req_total
+
+
+def walk_answers_cpu(buf, sess_off, slot_off, req_off, head_bits, states=None, resume: bool = False, max_headers: int = 16,
+                     flags: int = 0, bytes_size: int | None = None, n_slots_total: int | None = None,
+                     n_req_total: int | None = None, slot_req: bool = True):
+    """rhp_cpu_walk_answers (include/rhp_host.h).  Arguments as walk_responses_cpu, the queue (req_off, head_bits;
+    n_req_total: the host's copy, default req_off[-1]) and, for a round of the resumed walk, `states`
+    (WALK_STATE_DTYPE [n_sessions]) or resume=True (all-zero states).  Nothing passed in is changed.  Returns the
+    walk's tuple -- walk_responses_cpu's five, or walk_resume_cpu's six -- and behind it answered (u32 [n_sessions])
+    and slot_req (u32 [n_slots_total]; None with slot_req=False); both held WALK_POISON before the call."""
+    buf = np.array(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    req_off, head_bits, nq = _walk_asked(req_off, head_bits, n_req_total)
+    ns = len(sess_off) - 1
+    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    resume = resume or states is not None
+    st = _walk_states(states, ns) if resume else None
+    res = np.full(max(16 * ns, 1), WALK_POISON, dtype=np.uint8)
+    slots = np.full(max(32 * nt, 1), WALK_POISON, dtype=np.uint8)
+    msgs = np.full(max(16 * nt, 1), WALK_POISON, dtype=np.uint8)
+    hdrs = np.full(max(8 * nt * max_headers, 1), WALK_POISON, dtype=np.uint8)
+    ans = np.full(max(4 * ns, 1), WALK_POISON, dtype=np.uint8)
+    sreq = np.full(max(4 * nt, 1), WALK_POISON, dtype=np.uint8) if slot_req else None
+    w = WalkBatch(_ptr(buf), _ptr(buf), buf.size if bytes_size is None else bytes_size, _ptr(sess_off), _ptr(slot_off), ns,
+                  nt, max_headers, flags, _ptr(msgs), _ptr(hdrs), _ptr(slots), _ptr(res))
+    x = WalkAsked(_ptr(req_off), _ptr(head_bits), nq, 0, _ptr(ans), _addr(sreq))
+    rc = host().rhp_cpu_walk_answers(ctypes.byref(w), _addr(st), ctypes.byref(x))
+    if rc != 0:
+        raise RuntimeError(f"rhp_cpu_walk_answers failed: {rc}")
+    out = _walk_result(res, slots, msgs, hdrs, buf, ns, nt, max_headers)
+    if resume:
+        out += (st[: 32 * ns].view(WALK_STATE_DTYPE),)
+    return out + (ans[: 4 * ns].view(np.uint32), sreq[: 4 * nt].view(np.uint32) if slot_req else None)
+
+
+def walk_answers_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sessions: int, n_slots_total: int,
+                        max_headers: int, flags: int, msgs_t, hdrs_t, slots_t, results_t, states_t, req_off_t, head_bits_t,
+                        n_req_total: int, answered_t, slot_req_t, stream=None):
+    """One rhp_walk_answers call over device tensors on the stream (default: the current one): the tensors of
+    walk_resume_device (states_t None: the one-shot walk), req_off_t (i32 / u32 [n_sessions + 1]), head_bits_t (i32 /
+    u32 words), answered_t (u8, 4 * n_sessions bytes) and slot_req_t (u8, 4 * n_slots_total bytes, or None), all
+    4-byte aligned.  Nothing is synchronised or copied."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    w = WalkBatch(_addr(bytes_t), _addr(bytes_t), bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions,
+                  n_slots_total, max_headers, flags, _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+    x = WalkAsked(_addr(req_off_t), _addr(head_bits_t), n_req_total, 0, _addr(answered_t), _addr(slot_req_t))
+    rc = lib().rhp_walk_answers(ctypes.byref(w), _addr(states_t), ctypes.byref(x), ctypes.c_void_p(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_walk_answers failed: {rc}")
+
+
+def walk_answers_gpu(buf, sess_off, slot_off, req_off, head_bits, states=None, resume: bool = False, max_headers: int = 16,
+                     flags: int = 0, guard: int = 0, fill: int = WALK_POISON, bytes_size: int | None = None,
+                     n_slots_total: int | None = None, n_req_total: int | None = None, slot_req: bool = True):
+    """The call on the GPU.  bytes, msgs, hdrs, slots, results, states, req_off, head_bits, answered and slot_req
+    are Guarded device buffers (guard bytes on both sides, checked after the call); the records, answered and
+    slot_req hold `fill` first.  `states`: as walk_resume_gpu takes them (a Guarded buffer an earlier round returned
+    is used as it lies on the device); resume=True with states None: all-zero states.  Returns what
+    walk_answers_cpu returns; with states, the Guarded states buffer for the next round comes last."""
+    import torch
+    buf = np.array(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    req_off, head_bits, nq = _walk_asked(req_off, head_bits, n_req_total)
+    ns = len(sess_off) - 1
+    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    resume = resume or states is not None
+    db = Guarded("bytes", buf.size, guard, data=buf)
+    gm = Guarded("msgs", max(16 * nt, 1), guard, fill=fill)
+    gh = Guarded("hdrs", max(8 * nt * max_headers, 1), guard, fill=fill)
+    gs = Guarded("slots", max(32 * nt, 1), guard, fill=fill)
+    gr = Guarded("results", max(16 * ns, 1), guard, fill=fill)
+    gt = None
+    if resume:
+        gt = states if isinstance(states, Guarded) else Guarded("states", max(32 * ns, 1), guard, data=_walk_states(states, ns))
+    gq = Guarded("req_off", 4 * req_off.size, guard, data=req_off.view(np.uint8).copy())
+    gb = Guarded("head_bits", 4 * head_bits.size, guard, data=head_bits.view(np.uint8).copy())
+    ga = Guarded("answered", max(4 * ns, 4), guard, fill=fill)
+    gl = Guarded("slot_req", max(4 * nt, 4), guard, fill=fill) if slot_req else None
+    dso = torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda")
+    dsl = torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda")
+    walk_answers_device(db.view, buf.size if bytes_size is None else bytes_size, dso, dsl, ns, nt, max_headers, flags,
+                        gm.view, gh.view, gs.view, gr.view, gt.view if resume else None, gq.view, gb.view, nq, ga.view,
+                        gl.view if slot_req else None)
+    torch.cuda.synchronize()
+    if guard:
+        for g in (db, gm, gh, gs, gr, gq, gb, ga) + ((gt,) if resume else ()) + ((gl,) if slot_req else ()):
+            g.check()
+    out = _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
+                       db.view.cpu().numpy(), ns, nt, max_headers)
+    if resume:
+        out += (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE),)
+    out += (ga.view.cpu().numpy()[: 4 * ns].view(np.uint32), gl.view.cpu().numpy()[: 4 * nt].view(np.uint32) if slot_req else None)
+    return out + ((gt,) if resume else ())
 
 
 # The header lookup over the slots of a walk (rhp.h rhp_lookup_walked): the records stay where the walk left

@@ -583,7 +583,8 @@ extern "C" int rhp_cpu_walk_responses(const rhp_walk_batch_t *w)
     uint64_t lo = w->slot_off[s], hi = w->slot_off[s + 1];
     if (lo > hi || hi > w->n_slots_total) hi = lo = 0;   /* owns no slot */
     rhp_walk_result_t r;
-    walk_session_t(io, a, e, (uint32_t) lo, (uint32_t) hi, w->max_headers, w->flags, &r);
+    NobodyAsked nobody;
+    walk_session_t(io, a, e, (uint32_t) lo, (uint32_t) hi, w->max_headers, w->flags, &r, nobody);
     w->results[s] = r;
   }
   return 0;
@@ -605,8 +606,39 @@ extern "C" int rhp_cpu_walk_resume(const rhp_walk_batch_t *w, rhp_walk_state_t *
     rhp_walk_state_t st;
     memcpy(&st, &states[s], sizeof st);   /* (any alignment) */
     rhp_walk_result_t r;
-    if (walk_resume_t(io, a, e, (uint32_t) lo, (uint32_t) hi, w->max_headers, w->flags, &st, &r)) memcpy(&states[s], &st, sizeof st);
+    NobodyAsked nobody;
+    if (walk_resume_t(io, a, e, (uint32_t) lo, (uint32_t) hi, w->max_headers, w->flags, &st, &r, nobody)) memcpy(&states[s], &st, sizeof st);
     w->results[s] = r;
+  }
+  return 0;
+}
+
+/* rhp_walk_answers (rhp.h) on the host: either walk above with the kernels'
+ * policy (rhp_scalar.h Asked) over the session's queue, clamped as the kernels
+ * clamp it (rhp_walk_args.h rhp_walk_queue), with the launcher's argument check */
+extern "C" int rhp_cpu_walk_answers(const rhp_walk_batch_t *w, rhp_walk_state_t *states, const rhp_walk_asked_t *x)
+{
+  const int rc = rhp_walk_answers_check(w, states, x, 0);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  HostWalkIO io{w, rhp_walk_readable(w->bytes_size)};
+  for (uint32_t s = 0; s < w->n_sessions; s++) {
+    uint64_t a = w->sess_off[s], e = w->sess_off[s + 1];
+    a = a < io.lim ? a : io.lim;
+    e = e < a ? a : e < io.lim ? e : io.lim;
+    uint64_t lo = w->slot_off[s], hi = w->slot_off[s + 1];
+    if (lo > hi || hi > w->n_slots_total) hi = lo = 0;   /* owns no slot */
+    Asked ask = {x->head_bits, x->slot_req, 0, 0, 0, ~0u, 0};
+    ask.nq = rhp_walk_queue(x->req_off[s], x->req_off[s + 1], x->n_req_total, &ask.q0);
+    rhp_walk_result_t r;
+    if (states) {
+      rhp_walk_state_t st;
+      memcpy(&st, &states[s], sizeof st);   /* (any alignment) */
+      if (walk_resume_t(io, a, e, (uint32_t) lo, (uint32_t) hi, w->max_headers, w->flags, &st, &r, ask)) memcpy(&states[s], &st, sizeof st);
+    } else {
+      walk_session_t(io, a, e, (uint32_t) lo, (uint32_t) hi, w->max_headers, w->flags, &r, ask);
+    }
+    w->results[s] = r;
+    x->answered[s] = ask.k;
   }
   return 0;
 }

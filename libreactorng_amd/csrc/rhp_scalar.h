@@ -1047,6 +1047,56 @@ struct WalkStore {
  * say.  The reference has no rule for it; the walk's one invented rule. */
 RHP_HD bool status_has_no_body(uint32_t status) { return status - 100u < 100u || status == 204u || status == 304u; }
 
+/* What the walk is told about the requests its responses answer (rhp.h
+ * rhp_walk_answers), a policy of walk_message_t:
+ *   head()                whether the request the next final response answers
+ *                         was a HEAD: its reply has no body whatever its
+ *                         headers say (RFC 9112 6.3 item 1).  The walk's second
+ *                         invented rule; the reference has no response walker.
+ *                         Asked once per message, before its head is parsed.
+ *   answers(slot, final)  `slot` holds a head with result 1; a final one (no
+ *                         1xx) answers a request, an interim one precedes it
+ *   none(slot)            `slot` holds no such head: a continuation, a slot
+ *                         that stopped with HEAD or BAD
+ * Nobody asked: rhp_walk_responses and rhp_walk_resume, which compile to what
+ * they were without the policy. */
+struct NobodyAsked {
+  RHP_HDM bool head() const { return false; }
+  RHP_HDM void answers(uint32_t, bool) const {}
+  RHP_HDM void none(uint32_t) const {}
+};
+
+/* rhp_walk_answers' policy over the session's queue: the requests [q0, q0 +
+ * nq) of head_bits (clamped by the caller, rhp_walk_args.h rhp_walk_queue), k
+ * of them answered so far.  The word of head_bits that holds request q0 + k is
+ * kept: one 4-byte load per 32 requests, none for k >= nq.  slot_req may be
+ * NULL.  Both the kernels and the host twin use it as it stands. */
+struct Asked {
+  const uint32_t *head_bits;
+  uint32_t *slot_req;
+  uint32_t q0, nq, k;
+  uint32_t have, word;   /* head_bits[have] == word; have == ~0u: none loaded (no word has that index) */
+  RHP_HDM bool head()
+  {
+    if (k >= nq) return false;
+    const uint32_t q = q0 + k;
+    if ((q >> 5) != have) {
+      have = q >> 5;
+      word = head_bits[have];
+    }
+    return (word >> (q & 31u)) & 1u;
+  }
+  RHP_HDM void answers(uint32_t slot, bool final)
+  {
+    if (slot_req) slot_req[slot] = k;
+    if (final) k++;
+  }
+  RHP_HDM void none(uint32_t slot) const
+  {
+    if (slot_req) slot_req[slot] = RHP_WALK_REQ_NONE;
+  }
+};
+
 /* What a walk that takes the bytes of a started body (rhp_walk_resume) has to
  * remember of it: the phase the next round starts in and, of a Content-Length
  * body, the bytes still to come, of a chunked one the decoder's fields as
@@ -1072,12 +1122,15 @@ struct WalkCarry {
  *   io.hdrs(slot, at) a record view (HdrsRec's members) of the slot's header
  *                     records as just written, for the message at `at`
  *   io.move(at)       decode_chunked_t's Move over the bytes at `at` (RHP_WALK_DEFRAME)
- *   io.slot(slot, x)  slots[slot] = x */
-template <bool TAKE, class IO>
+ *   io.slot(slot, x)  slots[slot] = x
+ * ask (NobodyAsked, Asked) says which final responses answer a HEAD and hears
+ * what each slot turned out to be. */
+template <bool TAKE, class IO, class ASK>
 RHP_HD uint32_t walk_message_t(IO &io, uint64_t &pos, uint64_t e, uint32_t slot, uint32_t max_headers, uint32_t flags,
-                               WalkCarry &c)
+                               WalkCarry &c, ASK &ask)
 {
   const bool trailers = (flags & RHP_WALK_TRAILERS) != 0;
+  const bool asked_head = ask.head();   /* before the parse: its one load in 32 requests is under way while the head is read */
   uint32_t stop = RHP_WALK_END;
   rhp_walk_slot_t x;
   x.start = pos; x.body_len = 0; x.wire_len = 0; x.result = 1; x.body_kind = RHP_FRAME_NONE;
@@ -1092,8 +1145,8 @@ RHP_HD uint32_t walk_message_t(IO &io, uint64_t &pos, uint64_t e, uint32_t slot,
     x.result = frame_of_records_t(io.hdrs(slot, pos), o.st.m.num_headers, &x.body_kind, &x.body_len);
     if (x.result != 1) {
       stop = RHP_WALK_BAD;   /* (frame_of_values left RHP_FRAME_NONE, 0) */
-    } else if (status_has_no_body(o.st.m.status)) {
-      x.body_len = 0;
+    } else if (status_has_no_body(o.st.m.status) || asked_head) {
+      x.body_len = 0;   /* (a HEAD's reply: the same shape) */
     } else if (x.body_kind == RHP_FRAME_LENGTH) {
       x.wire_len = x.body_len > avail ? avail : x.body_len;
       if (x.body_len > avail) {
@@ -1146,14 +1199,16 @@ RHP_HD uint32_t walk_message_t(IO &io, uint64_t &pos, uint64_t e, uint32_t slot,
     else if (TAKE && (stop == RHP_WALK_BODY || stop == RHP_WALK_CLOSE)) pos = e;
   }
   io.slot(slot, x);
+  if (ret > 0 && x.result == 1) ask.answers(slot, o.st.m.status - 100u >= 100u);
+  else ask.none(slot);
   return stop;
 }
 
 /* the walk's loop over heads from pos on: a message per slot until the bytes,
  * the slots or a stop end it */
-template <bool TAKE, class IO>
+template <bool TAKE, class IO, class ASK>
 RHP_HD uint32_t walk_heads_t(IO &io, uint64_t &pos, uint64_t e, uint32_t &slot, uint32_t slot_hi, uint32_t max_headers,
-                             uint32_t flags, WalkCarry &c)
+                             uint32_t flags, WalkCarry &c, ASK &ask)
 {
   uint32_t stop = RHP_WALK_END;
   while (pos < e) {
@@ -1161,7 +1216,7 @@ RHP_HD uint32_t walk_heads_t(IO &io, uint64_t &pos, uint64_t e, uint32_t &slot, 
       stop = RHP_WALK_MORE;
       break;
     }
-    stop = walk_message_t<TAKE>(io, pos, e, slot, max_headers, flags, c);
+    stop = walk_message_t<TAKE>(io, pos, e, slot, max_headers, flags, c, ask);
     slot++;
     if (stop != RHP_WALK_END) break;
   }
@@ -1169,16 +1224,17 @@ RHP_HD uint32_t walk_heads_t(IO &io, uint64_t &pos, uint64_t e, uint32_t &slot, 
 }
 
 /* The walk of rhp.h (rhp_walk_responses) over the session [a, e) (both clamped
- * by the caller) that owns the slots [slot_lo, slot_hi).  The kernel
- * (rhp_walk.hip) and the host twin (rhp_host.cpp) instantiate it. */
-template <class IO>
+ * by the caller) that owns the slots [slot_lo, slot_hi), and with an Asked
+ * policy the walk of rhp_walk_answers.  The kernels (rhp_walk.hip) and the host
+ * twins (rhp_host.cpp) instantiate it. */
+template <class IO, class ASK>
 RHP_HD void walk_session_t(IO &io, uint64_t a, uint64_t e, uint32_t slot_lo, uint32_t slot_hi, uint32_t max_headers,
-                           uint32_t flags, rhp_walk_result_t *out)
+                           uint32_t flags, rhp_walk_result_t *out, ASK &ask)
 {
   uint64_t pos = a;
   uint32_t slot = slot_lo;
   WalkCarry none;   /* (never touched) */
-  const uint32_t stop = walk_heads_t<false>(io, pos, e, slot, slot_hi, max_headers, flags, none);
+  const uint32_t stop = walk_heads_t<false>(io, pos, e, slot, slot_hi, max_headers, flags, none, ask);
   out->n_slots = slot - slot_lo;
   out->stop = stop;
   out->consumed = pos - a;
@@ -1190,10 +1246,11 @@ RHP_HD void walk_session_t(IO &io, uint64_t a, uint64_t e, uint32_t slot_lo, uin
  * continuation slot of a body that an earlier round left open, then
  * walk_heads_t taking the bytes of a started body.  Returns whether *state,
  * rewritten whole, is to be stored: not for a corrupt or dead state, an empty
- * round or a continuation with no slot, which keep the state as it lies. */
-template <class IO>
+ * round or a continuation with no slot, which keep the state as it lies (and
+ * have not touched ask). */
+template <class IO, class ASK>
 RHP_HD bool walk_resume_t(IO &io, uint64_t a, uint64_t e, uint32_t slot_lo, uint32_t slot_hi, uint32_t max_headers,
-                          uint32_t flags, rhp_walk_state_t *state, rhp_walk_result_t *out)
+                          uint32_t flags, rhp_walk_state_t *state, rhp_walk_result_t *out, ASK &ask)
 {
   const uint32_t phase = state->phase;
   out->n_slots = 0;
@@ -1272,9 +1329,10 @@ RHP_HD bool walk_resume_t(IO &io, uint64_t a, uint64_t e, uint32_t slot_lo, uint
     }
     pos = a + x.wire_len;
     io.slot(slot, x);
+    ask.none(slot);   /* a continuation answers nothing: its head was counted in its own round */
     slot++;
   }
-  if (stop == RHP_WALK_END) stop = walk_heads_t<true>(io, pos, e, slot, slot_hi, max_headers, flags, c);
+  if (stop == RHP_WALK_END) stop = walk_heads_t<true>(io, pos, e, slot, slot_hi, max_headers, flags, c, ask);
   if (stop == RHP_WALK_BAD) c.phase = RHP_WALK_DEAD;
   rhp_walk_state_t n = {};
   n.phase = c.phase;

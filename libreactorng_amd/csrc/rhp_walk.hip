@@ -1,7 +1,8 @@
 /*
  * rhp_walk.hip -- rhp_walk_responses (rhp.h): the pipelined responses of a
- * batch of upstream connections walked in HBM, and rhp_walk_resume, the same
- * walk carried from round to round by a 32-byte state per session.  gfx950.
+ * batch of upstream connections walked in HBM, rhp_walk_resume, the same
+ * walk carried from round to round by a 32-byte state per session, and
+ * rhp_walk_answers, either of them told which requests were HEAD.  gfx950.
  *
  * One session per lane, one launch: the lane runs the walk's one statement
  * (rhp_scalar.h walk_session_t) -- the code the host twin runs over plain
@@ -112,7 +113,8 @@ __global__ __launch_bounds__(256) void rhp_walk_kernel(WParams p)
   if (lo > hi || hi > p.n_slots_total) hi = lo = 0;   /* owns no slot */
   DevWalkIO io{p};
   rhp_walk_result_t r;
-  walk_session_t(io, a, e, (uint32_t) lo, (uint32_t) hi, p.max_headers, p.flags, &r);
+  NobodyAsked nobody;
+  walk_session_t(io, a, e, (uint32_t) lo, (uint32_t) hi, p.max_headers, p.flags, &r, nobody);
   static_assert(sizeof(rhp_walk_result_t) == 16, "a result is one 16-byte store");
   u32x4 w;
   __builtin_memcpy(&w, &r, 16);
@@ -148,7 +150,8 @@ __global__ __launch_bounds__(256) void rhp_walk_resume_kernel(RParams q)
   __builtin_memcpy(&st, sw, 32);
   DevWalkIO io{p};
   rhp_walk_result_t r;
-  if (walk_resume_t(io, a, e, (uint32_t) lo, (uint32_t) hi, p.max_headers, p.flags, &st, &r)) {
+  NobodyAsked nobody;
+  if (walk_resume_t(io, a, e, (uint32_t) lo, (uint32_t) hi, p.max_headers, p.flags, &st, &r, nobody)) {
     __builtin_memcpy(sw, &st, 32);
     sp[0] = sw[0];
     sp[1] = sw[1];
@@ -156,6 +159,60 @@ __global__ __launch_bounds__(256) void rhp_walk_resume_kernel(RParams q)
   u32x4 w;
   __builtin_memcpy(&w, &r, 16);
   *reinterpret_cast<u32x4 *>(p.results + s) = w;
+}
+
+/* rhp_walk_answers: either walk above with the Asked policy (rhp_scalar.h)
+ * over the session's queue, RESUME choosing which -- two kernels, the same lane
+ * per session.  The lane reads its req_off pair, keeps the current head_bits
+ * word in a register (one 4-byte load per 32 requests of its queue, none
+ * outside the clamped queue) and stores answered[s] and the slot_req entries of
+ * the slots it wrote as plain 4-byte stores. */
+struct AParams {
+  WParams w;
+  rhp_walk_state_t *states;   /* RESUME */
+  const uint32_t *req_off, *head_bits;
+  uint32_t *answered, *slot_req;
+  uint32_t n_req_total;
+};
+
+template <bool RESUME>
+__global__ __launch_bounds__(256) void rhp_walk_answers_kernel(AParams q)
+{
+  const WParams &p = q.w;
+  const uint64_t t = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+  if (t >= p.n_sessions) return;
+  const uint32_t s = (uint32_t) t;
+  uint64_t a = p.sess_off[s], e = p.sess_off[s + 1];
+  a = a < p.lim ? a : p.lim;
+  e = e < a ? a : e < p.lim ? e : p.lim;
+  uint64_t lo = p.slot_off[s], hi = p.slot_off[s + 1];
+  if (lo > hi || hi > p.n_slots_total) hi = lo = 0;   /* owns no slot */
+  Asked ask;
+  ask.head_bits = q.head_bits;
+  ask.slot_req = q.slot_req;
+  ask.nq = rhp_walk_queue(q.req_off[s], q.req_off[s + 1], q.n_req_total, &ask.q0);
+  ask.k = 0;
+  ask.have = ~0u;
+  ask.word = 0;
+  DevWalkIO io{p};
+  rhp_walk_result_t r;
+  if (RESUME) {
+    u32x4 *sp = reinterpret_cast<u32x4 *>(q.states + s);
+    u32x4 sw[2] = {sp[0], sp[1]};
+    rhp_walk_state_t st;
+    __builtin_memcpy(&st, sw, 32);
+    if (walk_resume_t(io, a, e, (uint32_t) lo, (uint32_t) hi, p.max_headers, p.flags, &st, &r, ask)) {
+      __builtin_memcpy(sw, &st, 32);
+      sp[0] = sw[0];
+      sp[1] = sw[1];
+    }
+  } else {
+    walk_session_t(io, a, e, (uint32_t) lo, (uint32_t) hi, p.max_headers, p.flags, &r, ask);
+  }
+  u32x4 w;
+  __builtin_memcpy(&w, &r, 16);
+  *reinterpret_cast<u32x4 *>(p.results + s) = w;
+  q.answered[s] = ask.k;
 }
 
 }  // namespace
@@ -198,5 +255,17 @@ extern "C" int rhp_walk_resume(const rhp_walk_batch_t *b, rhp_walk_state_t *stat
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((uint32_t) (((uint64_t) b->n_sessions + 255u) / 256u));
   hipLaunchKernelGGL(rhp_walk_resume_kernel, grid, dim3(256), 0, s, q);
+  return (int) hipGetLastError();
+}
+
+extern "C" int rhp_walk_answers(const rhp_walk_batch_t *b, rhp_walk_state_t *states, const rhp_walk_asked_t *x, void *stream)
+{
+  const int rc = rhp_walk_answers_check(b, states, x, 1);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  const AParams q = {walk_params(b), states, x->req_off, x->head_bits, x->answered, x->slot_req, x->n_req_total};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((uint32_t) (((uint64_t) b->n_sessions + 255u) / 256u));
+  if (states) hipLaunchKernelGGL(rhp_walk_answers_kernel<true>, grid, dim3(256), 0, s, q);
+  else hipLaunchKernelGGL(rhp_walk_answers_kernel<false>, grid, dim3(256), 0, s, q);
   return (int) hipGetLastError();
 }

@@ -1,9 +1,9 @@
 /*
- * rhp_walk_args.h -- the argument rules of rhp_walk_responses and
- * rhp_walk_resume (rhp.h), one statement of them for the kernels' launchers
- * (rhp_walk.hip) and the host twins (rhp_host.cpp rhp_cpu_walk_responses,
- * rhp_cpu_walk_resume), with the two clamps all apply to whatever sess_off and
- * slot_off hold.
+ * rhp_walk_args.h -- the argument rules of rhp_walk_responses,
+ * rhp_walk_resume and rhp_walk_answers (rhp.h), one statement of them for the
+ * kernels' launchers (rhp_walk.hip) and the host twins (rhp_host.cpp
+ * rhp_cpu_walk_responses, rhp_cpu_walk_resume, rhp_cpu_walk_answers), with the
+ * clamps all apply to whatever sess_off, slot_off and req_off hold.
  */
 #ifndef RHP_WALK_ARGS_H
 #define RHP_WALK_ARGS_H
@@ -46,6 +46,40 @@ static inline int rhp_walk_resume_check(const rhp_walk_batch_t *w, const rhp_wal
   if (!states) return -22;
   if (device_pointers && ((uintptr_t) states & 15u) != 0) return -22;
   return 0;
+}
+
+/* rhp_walk_answers (rhp.h): the answers of the walk it runs -- rhp_walk_check
+ * with states == NULL, rhp_walk_resume_check with states -- and its own rules
+ * about the queue, for its launcher (rhp_walk.hip) and its host twin
+ * (rhp_host.cpp rhp_cpu_walk_answers); the four arrays are 4-byte accesses */
+static inline int rhp_walk_answers_check(const rhp_walk_batch_t *w, const rhp_walk_state_t *states, const rhp_walk_asked_t *x,
+                                         int device_pointers)
+{
+  const int rc = states ? rhp_walk_resume_check(w, states, device_pointers) : rhp_walk_check(w, device_pointers);
+  if (rc < 0) return rc;
+  if (!x || x->reserved != 0) return -22;
+  if (rc != 0) return rc;
+  if (!x->req_off || !x->answered) return -22;
+  if (x->n_req_total > 0 && !x->head_bits) return -22;
+  if (device_pointers &&
+      (((uintptr_t) x->req_off | (uintptr_t) x->head_bits | (uintptr_t) x->answered | (uintptr_t) x->slot_req) & 3u) != 0)
+    return -22;
+  return 0;
+}
+
+/* the queue session s owns, from its req_off pair: the requests [*q0, *q0 +
+ * nq), nq returned; a pair that is not ordered or reaches beyond n_req_total
+ * owns no request, so no bit at or beyond n_req_total is ever looked at */
+#if defined(__HIPCC__)
+#define RHP_WALK_HD __host__ __device__ __forceinline__
+#else
+#define RHP_WALK_HD static inline
+#endif
+RHP_WALK_HD uint32_t rhp_walk_queue(uint32_t lo, uint32_t hi, uint32_t n_req_total, uint32_t *q0)
+{
+  if (lo > hi || hi > n_req_total) hi = lo = 0;
+  *q0 = lo;
+  return hi - lo;
 }
 
 /* where a session has to end, and where the reader's zeros begin: bytes_size

@@ -1,0 +1,305 @@
+/*
+ * walk_answers_host_test.c -- rhp_cpu_walk_answers (include/rhp_host.h) under
+ * ASan/UBSan: a stand-alone program over rhp_host.cpp, rhp_emu.cpp and
+ * rhp_gen.c (the `walk-answers-asan` rule of libreactorng_amd/csrc/Makefile
+ * builds and runs it).
+ *
+ * It reads tests/golden/walk_answers.npz (argv[1], or the path from csrc/): the
+ * rounds of the sets of tests/walk_answer_sets.py with the answers over the
+ * compiled reference, written flat and uncompressed by
+ * tests/golden/make_golden_walk_answers.py, whose header names the arrays.
+ * Every set's rounds are run as a chain -- the states carried from round to
+ * round where the set has states, the queues as the file holds them, which is
+ * the round before's less its answered requests -- with and without
+ * RHP_WALK_DEFRAME and with and without slot_req.  Every buffer is allocated at
+ * exactly its documented size -- the round's bytes with their RHP_PAD, sess_off,
+ * slot_off and req_off [n_sessions + 1], head_bits [(n_req_total + 31) / 32],
+ * msgs, slots, slot_req [n_slots_total], hdrs [n_slots_total * max_headers],
+ * results, states and answered [n_sessions] -- and the outputs hold 0xC3 first;
+ * the sanitizer sees any access outside a buffer.  Then req_off rows that hold
+ * anything, and the refusals.  Exits non-zero on the first mismatch.
+ */
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "rhp.h"
+#include "rhp_host.h"
+
+#define FAIL(...) do { printf("walk_answers_host_test: " __VA_ARGS__); printf("\n"); return 1; } while (0)
+
+static uint8_t *g_file;
+static size_t g_size;
+
+static uint32_t rd16(const uint8_t *p) { return (uint32_t) p[0] | (uint32_t) p[1] << 8; }
+static uint32_t rd32(const uint8_t *p) { return rd16(p) | rd16(p + 2) << 16; }
+static uint64_t rd64(const uint8_t *p) { return (uint64_t) rd32(p) | (uint64_t) rd32(p + 4) << 32; }
+
+/* The data of member `name`.npy of the stored (not compressed) zip in g_file,
+ * copied into an allocation of exactly its size; *count = its elements of
+ * `elem` bytes, whose dtype string must be `descr`.  NULL: not found / not
+ * understood. */
+static void *npz_array(const char *name, const char *descr, size_t elem, size_t *count)
+{
+  char want[64];
+  snprintf(want, sizeof want, "%s.npy", name);
+  size_t at = 0;
+  while (at + 30 <= g_size && rd32(g_file + at) == 0x04034b50u) {   /* a local file header */
+    const uint8_t *h = g_file + at;
+    const uint32_t flags = rd16(h + 6), method = rd16(h + 8), nlen = rd16(h + 26), xlen = rd16(h + 28);
+    uint64_t csize = rd32(h + 18), usize = rd32(h + 22);
+    if (at + 30 + nlen + xlen > g_size) return NULL;
+    const uint8_t *x = h + 30 + nlen;
+    for (uint32_t q = 0; q + 4 <= xlen;) {   /* zip64: the sizes are in the extra field */
+      const uint32_t id = rd16(x + q), len = rd16(x + q + 2);
+      if (q + 4 + len > xlen) return NULL;
+      if (id == 1 && len >= 16 && usize == 0xffffffffu) {
+        usize = rd64(x + q + 4);
+        csize = rd64(x + q + 12);
+      }
+      q += 4 + len;
+    }
+    const size_t data = at + 30 + nlen + xlen;
+    if ((flags & 8u) || method != 0 || csize != usize || csize > g_size - data) return NULL;
+    if (nlen == strlen(want) && memcmp(h + 30, want, nlen) == 0) {
+      const uint8_t *d = g_file + data;
+      if (usize < 12 || memcmp(d, "\x93NUMPY", 6) != 0) return NULL;
+      const size_t hl = d[6] == 1 ? 10 + rd16(d + 8) : 12 + rd32(d + 8);
+      if (hl > usize) return NULL;
+      char head[512];
+      const size_t tl = hl < sizeof head ? hl : sizeof head - 1;
+      memcpy(head, d, tl);
+      for (size_t i = 0; i < tl; i++) if (!head[i]) head[i] = ' ';
+      head[tl] = 0;
+      if (!strstr(head + 10, descr) || strstr(head + 10, "'fortran_order': True")) return NULL;
+      const size_t bytes = (size_t) usize - hl;
+      if (bytes % elem) return NULL;
+      *count = bytes / elem;
+      void *out = malloc(bytes ? bytes : 1);
+      if (out && bytes) memcpy(out, d + hl, bytes);
+      return out;
+    }
+    at = data + (size_t) csize;
+  }
+  return NULL;
+}
+
+#define LOAD(var, type, descr) \
+  size_t n_##var = 0; \
+  type *var = (type *) npz_array(#var, descr, sizeof(type), &n_##var); \
+  if (!var) FAIL("%s: array '%s' (%s) not found", path, #var, descr)
+
+static int all_poison(const void *p, size_t n)
+{
+  for (size_t i = 0; i < n; i++) if (((const uint8_t *) p)[i] != 0xC3) return 0;
+  return 1;
+}
+
+
+static rhp_walk_state_t state_of(const uint8_t *kept, const uint8_t *phase, const uint8_t *ct, const uint8_t *hex,
+                                 const uint8_t *st, const uint64_t *left, size_t q, rhp_walk_state_t in)
+{
+  if (kept[q]) return in;
+  rhp_walk_state_t s;
+  memset(&s, 0, sizeof s);
+  s.phase = phase[q];
+  if (s.phase == RHP_WALK_IN_LENGTH) s.left = left[q];
+  if (s.phase == RHP_WALK_IN_CHUNKED) s.decoder.bytes_left_in_chunk = left[q];
+  s.decoder.consume_trailer = ct[q];
+  s.decoder.hex_count = hex[q];
+  s.decoder.state = st[q];
+  return s;
+}
+
+/* req_off rows that hold anything over head_bits at its exact size: every word set, so a bit read for a request
+ * the clamp does not own would show as a body not taken; the sanitizer sees a word read beyond the array */
+static int garbage(void)
+{
+  static const char kTwo[] = "HTTP/1.1 200 OK\r\nContent-Length: 2\r\n\r\nokHTTP/1.1 200 OK\r\nContent-Length: 2\r\n\r\nok";
+  enum { NS = 5, NT = 10, M = 2, LEN = sizeof kTwo - 1, NREQ = 40 };
+  static const uint32_t vals[] = {0, 1, 31, 32, 33, NREQ, NREQ + 1, 0xffffffffu, 0x80000000u, 7};
+  uint64_t seed = 99;
+  for (int trial = 0; trial < 300; trial++) {
+    uint8_t *buf = (uint8_t *) calloc(1, NS * LEN + RHP_PAD);
+    uint64_t so[NS + 1], sl[NS + 1];
+    uint32_t *ro = (uint32_t *) malloc(4 * (NS + 1)), *hb = (uint32_t *) malloc(4 * ((NREQ + 31) / 32));
+    uint32_t *ans = (uint32_t *) malloc(4 * NS), *sr = (uint32_t *) malloc(4 * NT);
+    rhp_msg_t *msgs = (rhp_msg_t *) malloc(sizeof(rhp_msg_t) * NT);
+    rhp_hdr_t *hdrs = (rhp_hdr_t *) malloc(sizeof(rhp_hdr_t) * NT * M);
+    rhp_walk_slot_t *slots = (rhp_walk_slot_t *) malloc(sizeof(rhp_walk_slot_t) * NT);
+    rhp_walk_result_t *res = (rhp_walk_result_t *) malloc(sizeof(rhp_walk_result_t) * NS);
+    rhp_walk_state_t *st = (rhp_walk_state_t *) calloc(NS, sizeof(rhp_walk_state_t));
+    memset(hb, 0xff, 4 * ((NREQ + 31) / 32));
+    for (int i = 0; i <= NS; i++) {
+      if (i < NS) memcpy(buf + i * LEN, kTwo, LEN);
+      so[i] = (uint64_t) i * LEN;
+      sl[i] = 2u * (uint64_t) i;
+      seed = seed * 6364136223846793005ull + 1442695040888963407ull;
+      ro[i] = vals[(seed >> 33) % (sizeof vals / sizeof vals[0])];
+    }
+    const rhp_walk_batch_t w = {buf, buf, NS * LEN + RHP_PAD, so, sl, NS, NT, M, 0, msgs, hdrs, slots, res};
+    const rhp_walk_asked_t x = {ro, hb, NREQ, 0, ans, (trial & 1) ? sr : NULL};
+    if (rhp_cpu_walk_answers(&w, (trial & 2) ? st : NULL, &x) != 0) FAIL("garbage trial %d: refused", trial);
+    for (int s = 0; s < NS; s++) {
+      const uint32_t nq = ro[s] <= ro[s + 1] && ro[s + 1] <= NREQ ? ro[s + 1] - ro[s] : 0;
+      /* every owned request is a HEAD: the first reply has no body, so "ok" is the next head and is malformed */
+      const uint32_t want_stop = nq ? RHP_WALK_BAD : RHP_WALK_END, want_ans = nq ? 1 : 2;
+      if (res[s].stop != want_stop || ans[s] != want_ans)
+        FAIL("garbage trial %d session %d (req_off %u, %u): stop %u answered %u", trial, s, ro[s], ro[s + 1], res[s].stop, ans[s]);
+    }
+    free(buf); free(ro); free(hb); free(ans); free(sr); free(msgs); free(hdrs); free(slots); free(res); free(st);
+  }
+  return 0;
+}
+
+static int refusals(void)
+{
+  uint8_t *bytes = (uint8_t *) calloc(1, 512);
+  uint64_t so[2] = {0, 0}, sl[2] = {0, 1};
+  uint32_t ro[2] = {0, 1}, hb[1] = {1}, ans[1], sr[1];
+  rhp_msg_t m;
+  rhp_hdr_t h[4];
+  rhp_walk_slot_t s;
+  rhp_walk_result_t r;
+  rhp_walk_state_t st;
+  memset(&st, 0, sizeof st);
+  const rhp_walk_batch_t ok = {bytes, bytes, 512, so, sl, 1, 1, 4, 0, &m, h, &s, &r};
+  const rhp_walk_asked_t xok = {ro, hb, 1, 0, ans, sr};
+  if (rhp_cpu_walk_answers(&ok, NULL, &xok) != 0 || rhp_cpu_walk_answers(&ok, &st, &xok) != 0) FAIL("a sound call was refused");
+  if (ans[0] != 0) FAIL("an empty session answered %u", ans[0]);
+  if (rhp_cpu_walk_answers(&ok, NULL, NULL) != -22 || rhp_cpu_walk_answers(NULL, NULL, &xok) != -22) FAIL("a NULL argument accepted");
+  rhp_walk_asked_t x = xok;
+  x.reserved = 1;
+  if (rhp_cpu_walk_answers(&ok, NULL, &x) != -22) FAIL("reserved != 0 accepted");
+  x = xok; x.req_off = NULL;
+  if (rhp_cpu_walk_answers(&ok, &st, &x) != -22) FAIL("NULL req_off accepted");
+  x = xok; x.answered = NULL;
+  if (rhp_cpu_walk_answers(&ok, NULL, &x) != -22) FAIL("NULL answered accepted");
+  x = xok; x.head_bits = NULL;
+  if (rhp_cpu_walk_answers(&ok, NULL, &x) != -22) FAIL("NULL head_bits with requests accepted");
+  x.n_req_total = 0; x.slot_req = NULL;
+  if (rhp_cpu_walk_answers(&ok, NULL, &x) != 0) FAIL("no request needs no head_bits, and slot_req may be NULL");
+  rhp_walk_batch_t b = ok;
+  b.flags = 8;
+  if (rhp_cpu_walk_answers(&b, NULL, &xok) != -22) FAIL("an unknown flag accepted");
+  b = ok; b.n_sessions = 0;
+  x = xok; x.req_off = NULL; x.answered = NULL; x.head_bits = NULL;
+  if (rhp_cpu_walk_answers(&b, NULL, &x) != 0) FAIL("an empty call needs no queue");
+  free(bytes);
+  return 0;
+}
+
+int main(int argc, char **argv)
+{
+  const char *path = argc > 1 ? argv[1] : "../../tests/golden/walk_answers.npz";
+  FILE *f = fopen(path, "rb");
+  if (!f) FAIL("cannot open %s", path);
+  fseek(f, 0, SEEK_END);
+  g_size = (size_t) ftell(f);
+  fseek(f, 0, SEEK_SET);
+  g_file = (uint8_t *) malloc(g_size);
+  if (!g_file || fread(g_file, 1, g_size, f) != g_size) FAIL("cannot read %s", path);
+  fclose(f);
+  LOAD(set_maxh, uint32_t, "<u4"); LOAD(set_flags, uint32_t, "<u4"); LOAD(set_nsess, uint32_t, "<u4"); LOAD(set_mode, uint32_t, "<u4");
+  LOAD(set_round, uint32_t, "<u4"); LOAD(set_first, uint32_t, "<u4"); LOAD(states_in, uint8_t, "|u1");
+  LOAD(round_q, uint32_t, "<u4"); LOAD(round_slot, uint32_t, "<u4"); LOAD(round_byte, uint64_t, "<u8");
+  LOAD(round_word, uint32_t, "<u4"); LOAD(round_nreq, uint32_t, "<u4"); LOAD(req_off, uint32_t, "<u4"); LOAD(head_words, uint32_t, "<u4");
+  LOAD(bytes, uint8_t, "|u1"); LOAD(defr_idx, uint32_t, "<u4"); LOAD(defr_val, uint8_t, "|u1");
+  LOAD(len, uint32_t, "<u4"); LOAD(cap, uint8_t, "|u1"); LOAD(n_slots, uint8_t, "|u1"); LOAD(stop, uint8_t, "|u1");
+  LOAD(consumed, uint32_t, "<u4"); LOAD(kept, uint8_t, "|u1"); LOAD(st_phase, uint8_t, "|u1"); LOAD(st_ct, uint8_t, "|u1");
+  LOAD(st_hex, uint8_t, "|u1"); LOAD(st_state, uint8_t, "|u1"); LOAD(st_left, uint64_t, "<u8"); LOAD(answered, uint8_t, "|u1");
+  LOAD(start, uint32_t, "<u4"); LOAD(body_len, uint64_t, "<u8"); LOAD(wire_len, uint32_t, "<u4"); LOAD(result, int8_t, "|i1");
+  LOAD(body_kind, uint8_t, "|u1"); LOAD(ret, int32_t, "<i4"); LOAD(slot_req, int16_t, "<i2");
+  const size_t S = n_set_maxh;
+  if (n_set_round != S + 1 || n_set_first != S + 1 || n_set_mode != S || n_len != n_stop || n_len != n_answered || n_start != n_ret ||
+      n_start != n_slot_req || n_defr_idx != n_defr_val || n_round_word != n_round_nreq + 1)
+    FAIL("%s: sizes", path);
+  uint8_t *deframed = (uint8_t *) malloc(n_bytes ? n_bytes : 1);
+  memcpy(deframed, bytes, n_bytes);
+  for (size_t i = 0; i < n_defr_idx; i++) deframed[defr_idx[i]] = defr_val[i];
+  size_t rounds_run = 0;
+  for (size_t s = 0; s < S; s++) {
+    const uint32_t n = set_nsess[s], maxh = set_maxh[s];
+    for (int variant = 0; variant < 4; variant++) {
+      const int deframe = variant & 1, with_sr = !(variant & 2);
+      rhp_walk_state_t *st = (rhp_walk_state_t *) calloc(n ? n : 1, sizeof(rhp_walk_state_t));
+      rhp_walk_state_t *in = (rhp_walk_state_t *) calloc(n ? n : 1, sizeof(rhp_walk_state_t));
+      if (set_first[s + 1] > set_first[s]) memcpy(st, states_in + 32 * (size_t) set_first[s], 32 * (size_t) n);
+      for (uint32_t r = set_round[s]; r < set_round[s + 1]; r++) {
+        const size_t q0 = round_q[r], nb = (size_t) (round_byte[r + 1] - round_byte[r]);
+        if (round_q[r + 1] - q0 != n || q0 + r + n + 1 > n_req_off) FAIL("set %zu round %u: sessions", s, r);
+        uint8_t *buf = (uint8_t *) calloc(1, nb + RHP_PAD);
+        memcpy(buf, bytes + round_byte[r], nb);
+        uint64_t *so = (uint64_t *) calloc(n + 1, 8), *sl = (uint64_t *) calloc(n + 1, 8);
+        uint32_t *ro = (uint32_t *) malloc(4 * (size_t) (n + 1));
+        memcpy(ro, req_off + q0 + r, 4 * (size_t) (n + 1));
+        for (uint32_t i = 0; i < n; i++) {
+          so[i + 1] = so[i] + len[q0 + i];
+          sl[i + 1] = sl[i] + cap[q0 + i];
+        }
+        const uint32_t nt = (uint32_t) sl[n], nreq = round_nreq[r], nw = (nreq + 31) / 32;
+        if (round_word[r + 1] - round_word[r] < nw) FAIL("set %zu round %u: head_bits words", s, r);
+        uint32_t *hb = (uint32_t *) malloc(4 * (size_t) (nw ? nw : 1));   /* exactly the documented words */
+        memcpy(hb, head_words + round_word[r], 4 * (size_t) nw);
+        rhp_msg_t *msgs = (rhp_msg_t *) malloc(sizeof(rhp_msg_t) * (nt ? nt : 1));
+        rhp_hdr_t *hdrs = (rhp_hdr_t *) malloc(sizeof(rhp_hdr_t) * (size_t) nt * maxh + 1);
+        rhp_walk_slot_t *slots = (rhp_walk_slot_t *) malloc(sizeof(rhp_walk_slot_t) * (nt ? nt : 1));
+        rhp_walk_result_t *res = (rhp_walk_result_t *) malloc(sizeof(rhp_walk_result_t) * n);
+        uint32_t *ans = (uint32_t *) malloc(4 * (size_t) n), *sr = (uint32_t *) malloc(4 * (size_t) (nt ? nt : 1));
+        memset(msgs, 0xC3, sizeof(rhp_msg_t) * nt);
+        memset(hdrs, 0xC3, sizeof(rhp_hdr_t) * (size_t) nt * maxh);
+        memset(slots, 0xC3, sizeof(rhp_walk_slot_t) * nt);
+        memset(res, 0xC3, sizeof(rhp_walk_result_t) * n);
+        memset(ans, 0xC3, 4 * (size_t) n);
+        memset(sr, 0xC3, 4 * (size_t) nt);
+        memcpy(in, st, sizeof(rhp_walk_state_t) * n);
+        const rhp_walk_batch_t w = {buf, buf, nb + RHP_PAD, so, sl, n, nt, maxh, set_flags[s] | (deframe ? RHP_WALK_DEFRAME : 0u),
+                                    msgs, hdrs, slots, res};
+        const rhp_walk_asked_t x = {ro, nw ? hb : NULL, nreq, 0, ans, with_sr ? sr : NULL};
+        if (rhp_cpu_walk_answers(&w, set_mode[s] ? st : NULL, &x) != 0) FAIL("set %zu round %u: refused", s, r);
+        size_t t = round_slot[r];
+        for (uint32_t i = 0; i < n; i++) {
+          const size_t q = q0 + i;
+          if (res[i].n_slots != n_slots[q] || res[i].stop != stop[q] || res[i].consumed != consumed[q] || ans[i] != answered[q])
+            FAIL("set %zu round %u session %u: result (%u, %u, %llu) answered %u, the reference's (%u, %u, %u) answered %u", s, r, i,
+                 res[i].n_slots, res[i].stop, (unsigned long long) res[i].consumed, ans[i], n_slots[q], stop[q], consumed[q], answered[q]);
+          for (uint32_t k = 0; k < cap[q]; k++) {
+            const size_t at = (size_t) sl[i] + k;
+            if (k >= n_slots[q]) {
+              if (!all_poison(&slots[at], sizeof slots[at]) || !all_poison(&msgs[at], sizeof msgs[at]) || !all_poison(&sr[at], 4) ||
+                  !all_poison(hdrs + at * maxh, sizeof(rhp_hdr_t) * maxh))
+                FAIL("set %zu round %u session %u: a record past n_slots was written", s, r, i);
+              continue;
+            }
+            const rhp_walk_slot_t *v = &slots[at];
+            if (v->start != start[t] || v->body_len != body_len[t] || v->wire_len != wire_len[t] || v->result != result[t] ||
+                v->body_kind != body_kind[t] || msgs[at].ret != ret[t])
+              FAIL("set %zu round %u session %u slot %u differs from the reference's", s, r, i, k);
+            if (with_sr ? sr[at] != (slot_req[t] < 0 ? RHP_WALK_REQ_NONE : (uint32_t) slot_req[t]) : !all_poison(&sr[at], 4))
+              FAIL("set %zu round %u session %u slot %u: slot_req %u, the reference's %d", s, r, i, k, sr[at], slot_req[t]);
+            t++;
+          }
+          if (set_mode[s]) {
+            const rhp_walk_state_t want = state_of(kept, st_phase, st_ct, st_hex, st_state, st_left, q, in[i]);
+            if (memcmp(&st[i], &want, sizeof want) != 0) FAIL("set %zu round %u session %u: the state differs from the reference's", s, r, i);
+          }
+        }
+        if (t != round_slot[r + 1]) FAIL("set %zu round %u: slots", s, r);
+        if (memcmp(buf, (deframe ? deframed : bytes) + round_byte[r], nb) != 0) FAIL("set %zu round %u (deframe %d): the bytes differ", s, r, deframe);
+        for (size_t i = nb; i < nb + RHP_PAD; i++) if (buf[i]) FAIL("set %zu round %u: the pad was written", s, r);
+        free(buf); free(so); free(sl); free(ro); free(hb); free(msgs); free(hdrs); free(slots); free(res); free(ans); free(sr);
+        rounds_run++;
+      }
+      free(st); free(in);
+    }
+  }
+  if (garbage() || refusals()) return 1;
+  printf("walk_answers_host_test OK: %zu sets, %zu rounds run\n", S, rounds_run);
+  free(deframed);
+  void *loaded[] = {set_maxh, set_flags, set_nsess, set_mode, set_round, set_first, states_in, round_q, round_slot, round_byte, round_word,
+                    round_nreq, req_off, head_words, bytes, defr_idx, defr_val, len, cap, n_slots, stop, consumed, kept, st_phase, st_ct,
+                    st_hex, st_state, st_left, answered, start, body_len, wire_len, result, body_kind, ret, slot_req, g_file};
+  for (size_t i = 0; i < sizeof loaded / sizeof loaded[0]; i++) free(loaded[i]);
+  return 0;
+}
