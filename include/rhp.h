@@ -1295,6 +1295,137 @@ typedef struct rhp_walk_lookup {
 
 int rhp_lookup_walked(const rhp_walk_batch_t *w, const rhp_walk_lookup_t *l, void *stream);
 
+/*
+ * The walked responses re-written for the client side: what a proxy does next
+ * with each upstream response is one call of the reference's writer,
+ *   http_write_response(&client->stream, status, date, type, body, fields, fields_count)
+ * (src/reactor/http.c:236-297), and this is that call for every slot of a walk
+ * that holds a whole response, from the records where they lie.  w is the batch
+ * exactly as rhp_walk_responses, rhp_walk_resume or rhp_walk_answers left it on
+ * `stream`.  For every slot i < n_slots_total, why[i] and out_off[i + 1] -
+ * out_off[i] are written; out_off is the exclusive prefix sum of the sizes.
+ *   Relayed.  Slot i is relayed -- why[i] == RHP_RELAY_OK -- when every test
+ *   below holds; otherwise its size is 0 and why[i] names the first that failed
+ *   (enum rhp_relay_why, in this order):
+ *     UNUSED    it is in use, NOT_HEAD a head, OUTSIDE and inside, the three
+ *               words as rhp_lookup_walked defines them (owner by the same
+ *               bisection; nothing of a slot not in use is read);
+ *     INTERIM   its status is not 100..199: interim heads are the proxy's own
+ *               business;
+ *     PARTIAL   it is not the session's last written slot (i - slot_off[s] + 1 ==
+ *               n_slots) of a round that stopped with RHP_WALK_BODY or
+ *               RHP_WALK_CLOSE: that body is not all there, the host streams it;
+ *     FOLD      none of its header records k < min(num_headers, max_headers) has
+ *               name_off == RHP_NAME_NULL: the reference's writer has no form for
+ *               an obs-fold line, such a head goes to the host;
+ *     SPAN      its phrase (msg_len > 0) and the name and value of every such
+ *               record lie inside [0, ret) (every parsed record does; a crafted
+ *               one that does not is never read through);
+ *     FRAMING   its body can be named: both lengths 0 whatever the kind (the
+ *               1xx/204/304 rule, a reply to a HEAD, RHP_WALK_NONE_EMPTY, an
+ *               empty body); RHP_FRAME_LENGTH with wire_len == body_len;
+ *               RHP_FRAME_CHUNKED only when w->flags has RHP_WALK_DEFRAME, the
+ *               body then being the first body_len bytes of the wire span;
+ *     LONG      body_len < 2^32 (the reference prints Content-Length with
+ *               http_u32_sprint);
+ *     BODY_OUTSIDE  [start + ret, start + ret + body_len) lies inside the
+ *               session and below the readable end (Memory, below).
+ *   Bytes.  A relayed slot's bytes are exactly what http_write_response
+ *   appends (the layout is rhp_write_responses', above) for
+ *     status  three decimal digits, those of msgs[i].status modulo 1000 with
+ *             leading zeros kept (a parsed status is below 1000; of a crafted
+ *             one above, the thousands are not printed, and the INTERIM test
+ *             looks at the whole value), and, when msg_len > 0, one SP and the
+ *             phrase bytes.  The digits are printed, not copied: the record
+ *             does not say where they stood;
+ *     type    the value of the first header whose name equals Content-Type;
+ *             empty when there is none;
+ *     body    as above;
+ *     fields  the head's header records in order, name and value bytes as they
+ *             lie, but for every record -- every match, not only the first --
+ *             whose name equals Content-Type, Content-Length, Transfer-Encoding
+ *             or one of the caller's n_names names (typically Connection,
+ *             Keep-Alive, Server, Date).
+ *   Names are equal under rhp_lookup_walked's fold: equal lengths and equal
+ *   bytes with a..z mapped to A..Z on both sides, no other byte.
+ *   THE REFERENCE HAS NO RULE HERE for four things, which are this call's
+ *   invented part: the fold above and which names are dropped; the status text
+ *   (printed digits, one SP, the phrase); the upstream's minor version is not
+ *   carried, the writer's text being "HTTP/1.1"; and a reply to a HEAD and a
+ *   304 go out with "Content-Length: 0", as a libreactor server would send
+ *   them, whatever the upstream's Content-Length said.  Everything else is the
+ *   reference's writer, byte for byte.
+ *   Order.  Slots are written in ascending index, so a session's replies are
+ *   contiguous: out[out_off[slot_off[s]], out_off[slot_off[s+1]]).
+ *   When out_off[n_slots_total] > out_size nothing is written to `out`; out_off
+ *   and why are still complete: grow and call again.
+ * Memory.  Nothing is read but what rhp_lookup_walked reads and, of a relayed
+ * slot, its body.  Phrase, names, values and bodies are read as the aligned
+ * dwords that hold them, so the BODY_OUTSIDE test bounds start + ret +
+ * body_len, rounded up to 4, by the readable end the walk clamps its sessions
+ * to (bytes_size rounded down to whole 16-byte lines, less one line), and the
+ * head lies below bytes_size rounded down to 4 as for the lookup.  Nothing is
+ * written outside out_off[0, n_slots_total], why[0, n_slots_total), work and
+ * out[0, out_off[n_slots_total]).
+ * -EINVAL (rhp_relay_args.h): whatever rhp_walk_responses refuses about w; a
+ * NULL r, out_off, why, date or work; date_len != RHP_DATE_LEN; n_names above
+ * RHP_RELAY_MAX_NAMES; a NULL text or names with n_names > 0; an empty name or
+ * one longer than RHP_CLASSIFY_NAME_MAX; a NULL out with out_size != 0; a NULL
+ * results with n_sessions > 0; out_off not 8-byte aligned, why not 4-byte
+ * aligned, work not 8-byte aligned (device pointers only).  n_slots_total == 0
+ * or n_sessions == 0 writes out_off[0] = 0 and nothing else.
+ * Launch contract as rhp_write_responses: four kernels on `stream` (sizes with
+ * tile sums, two scan passes, copy), asynchronous, no allocation, no copy, no
+ * synchronisation; the names and the date travel in the kernel argument and
+ * the caller's tables are free when the call returns; thread-safe.  The empty
+ * call (n_slots_total == 0 or n_sessions == 0) launches no kernel: its
+ * out_off[0] = 0 is one 8-byte hipMemsetAsync on `stream`, as
+ * rhp_write_responses' with n == 0.
+ */
+#define RHP_RELAY_MAX_NAMES (RHP_CLASSIFY_MAX_NAMES - 3u)   /* the three built-in names take the rest */
+
+enum rhp_relay_why { RHP_RELAY_OK = 0,        /* relayed */
+                     RHP_RELAY_UNUSED,        /* the walk did not write the slot */
+                     RHP_RELAY_NOT_HEAD,      /* a continuation slot, a HEAD or BAD stop slot */
+                     RHP_RELAY_OUTSIDE,       /* the head does not lie inside its session */
+                     RHP_RELAY_INTERIM,       /* status 100..199 */
+                     RHP_RELAY_PARTIAL,       /* the last slot of a BODY or CLOSE round */
+                     RHP_RELAY_FOLD,          /* an obs-fold line among the headers */
+                     RHP_RELAY_SPAN,          /* a phrase, name or value outside [0, ret) */
+                     RHP_RELAY_FRAMING,       /* the body cannot be named */
+                     RHP_RELAY_LONG,          /* body_len >= 2^32 */
+                     RHP_RELAY_BODY_OUTSIDE}; /* the body does not lie inside its session */
+
+typedef struct rhp_walk_relay {
+  const uint8_t    *text;       /* host: the bytes of the caller's drop names (as rhp_walk_lookup_t) */
+  const rhp_span_t *names;      /* host [n_names]: spans of `text` */
+  uint32_t          n_names;    /* 0 .. RHP_RELAY_MAX_NAMES */
+  uint32_t          date_len;   /* must be RHP_DATE_LEN */
+  const char       *date;       /* host, date_len bytes */
+  uint64_t         *out_off;    /* device [n_slots_total + 1]: exclusive prefix sum of the sizes, always written */
+  uint32_t         *why;        /* device [n_slots_total]: enum rhp_relay_why */
+  uint8_t          *out;        /* device, out_size bytes, any alignment */
+  uint64_t          out_size;   /* out_off[n_slots_total] > out_size: nothing is written to out */
+  uint64_t         *work;       /* device scratch, >= RHP_RELAY_WORK_WORDS(n_slots_total) u64 */
+} rhp_walk_relay_t;
+
+/* the tile sums of the scan, and per slot the plan the sizes step leaves the
+ * copy step: which header records are kept, and the type's value */
+#define RHP_RELAY_WORK_WORDS(n) (((uint64_t) (n) + 4095u) / 4096u + 1u + 2u * (uint64_t) (n))
+
+int rhp_relay_walked(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r, void *stream);
+
+/* For measuring, not for a reactor's round: rhp_relay_walked and
+ * rhp_write_responses with a HIP event recorded on `stream` before the sizes
+ * step, behind it, behind the two scan kernels and behind the copy step.  The
+ * call creates and destroys its four events, waits for the last one (a host
+ * synchronisation) and returns the three elapsed times in microseconds: us[0]
+ * sizes, us[1] scan, us[2] copy.  The same kernels, arguments, outputs and
+ * codes as the plain call; an empty call (no slot, n == 0) and a NULL us are
+ * -EINVAL.  tools/bench_walk_relay.py. */
+int rhp_relay_walked_steps(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r, void *stream, float us[3]);
+int rhp_write_responses_steps(const rhp_resp_batch_t *batch, void *stream, float us[3]);
+
 
 #ifdef __cplusplus
 }

@@ -178,6 +178,15 @@ int rhp_cpu_walk_answers(const rhp_walk_batch_t *w, rhp_walk_state_t *states /* 
  * and no record of a slot that is not in use.  Sequential. */
 int rhp_cpu_lookup_walked(const rhp_walk_batch_t *w, const rhp_walk_lookup_t *l);
 
+/* rhp_relay_walked (rhp.h) over a walk's records in host memory: every pointer
+ * of `w` and of `r` is host memory, of any alignment, and there is no stream.
+ * The same out_off, why and out and the same -22 (rhp_relay_args.h; the
+ * alignment rules are the device's alone).  work has to be there and is not
+ * touched.  Bytes are read one at a time: of the batch's bytes only the heads
+ * and bodies of relayed slots, and no record of a slot that is not in use.
+ * Sequential. */
+int rhp_cpu_relay_walked(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r);
+
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */
 typedef struct rhp_phr_header {
   const char *name;

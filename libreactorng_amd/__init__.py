@@ -67,7 +67,8 @@ SESSION_RESULT_DTYPE = np.dtype([("n_slots", "<u4"), ("more", "<u4"), ("consumed
 RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_version", "rhp_write_responses",
                "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
                "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages", "rhp_decode_chunked", "rhp_frame_messages",
-               "rhp_walk_responses", "rhp_walk_resume", "rhp_lookup_walked", "rhp_walk_answers")
+               "rhp_walk_responses", "rhp_walk_resume", "rhp_lookup_walked", "rhp_walk_answers", "rhp_relay_walked",
+               "rhp_relay_walked_steps", "rhp_write_responses_steps")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
@@ -76,7 +77,7 @@ HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_spl
                 "rhp_cpu_split_sessions", "rhp_cpu_parse_messages", "rhp_phr_parse_response", "rhp_phr_parse_headers",
                 "rhp_cpu_decode_chunked", "rhp_phr_decode_chunked", "rhp_phr_decode_chunked_is_in_data",
                 "rhp_cpu_frame_messages", "rhp_cpu_walk_responses", "rhp_cpu_walk_resume",
-                "rhp_cpu_lookup_walked", "rhp_cpu_walk_answers")
+                "rhp_cpu_lookup_walked", "rhp_cpu_walk_answers", "rhp_cpu_relay_walked")
 
 _rhp = None
 _host = None
@@ -246,6 +247,24 @@ WALK_REQ_NONE = 0xFFFFFFFF   # RHP_WALK_REQ_NONE
 assert ctypes.sizeof(WalkAsked) == 40
 
 
+class WalkRelay(ctypes.Structure):
+    """rhp_walk_relay_t (include/rhp.h): the drop names, the date and the outputs of rhp_relay_walked"""
+    _fields_ = [("text", ctypes.c_void_p), ("names", ctypes.c_void_p), ("n_names", ctypes.c_uint32),
+                ("date_len", ctypes.c_uint32), ("date", ctypes.c_char_p), ("out_off", ctypes.c_void_p),
+                ("why", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_size", ctypes.c_uint64), ("work", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(WalkRelay) == 72
+RELAY_MAX_NAMES = 13   # RHP_RELAY_MAX_NAMES
+(RELAY_OK, RELAY_UNUSED, RELAY_NOT_HEAD, RELAY_OUTSIDE, RELAY_INTERIM, RELAY_PARTIAL, RELAY_FOLD, RELAY_SPAN, RELAY_FRAMING,
+ RELAY_LONG, RELAY_BODY_OUTSIDE) = range(11)   # enum rhp_relay_why
+
+
+def relay_work_words(n: int) -> int:
+    """RHP_RELAY_WORK_WORDS (include/rhp.h)"""
+    return (n + 4095) // 4096 + 1 + 2 * n
+
+
 def _torch_hip_runtime() -> str | None:
     """Path of the HIP runtime torch ships (torch/lib/libamdhip64.so), found
     without importing torch."""
@@ -336,6 +355,12 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_walk_resume.restype = ctypes.c_int
         _rhp.rhp_lookup_walked.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkLookup), vp]
         _rhp.rhp_lookup_walked.restype = ctypes.c_int
+        _rhp.rhp_relay_walked.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkRelay), vp]
+        _rhp.rhp_relay_walked.restype = ctypes.c_int
+        _rhp.rhp_relay_walked_steps.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkRelay), vp, ctypes.POINTER(ctypes.c_float * 3)]
+        _rhp.rhp_relay_walked_steps.restype = ctypes.c_int
+        _rhp.rhp_write_responses_steps.argtypes = [ctypes.POINTER(RespBatch), vp, ctypes.POINTER(ctypes.c_float * 3)]
+        _rhp.rhp_write_responses_steps.restype = ctypes.c_int
         _rhp.rhp_walk_answers.argtypes = [ctypes.POINTER(WalkBatch), vp, ctypes.POINTER(WalkAsked), vp]
         _rhp.rhp_walk_answers.restype = ctypes.c_int
     return _rhp
@@ -414,6 +439,8 @@ def host() -> ctypes.CDLL:
         _host.rhp_cpu_walk_resume.restype = ctypes.c_int
         _host.rhp_cpu_lookup_walked.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkLookup)]
         _host.rhp_cpu_lookup_walked.restype = ctypes.c_int
+        _host.rhp_cpu_relay_walked.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkRelay)]
+        _host.rhp_cpu_relay_walked.restype = ctypes.c_int
         _host.rhp_cpu_walk_answers.argtypes = [ctypes.POINTER(WalkBatch), vp, ctypes.POINTER(WalkAsked)]
         _host.rhp_cpu_walk_answers.restype = ctypes.c_int
     return _host
@@ -2469,3 +2496,155 @@ def lookup_walked_gpu(buf, sess_off, slot_off, names, max_headers: int = 16, fla
     if gt is not None:
         out += (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE), gt)
     return _lookup_fields(gf.view.cpu().numpy(), nn, nt), out
+
+
+# The walked responses re-written for the client side (rhp.h rhp_relay_walked): the records stay where the walk
+# left them; out_off, why and the replies come back.
+
+RELAY_POISON = 0xC3   # what out_off, why and out hold before a call (tests)
+
+
+def _relay_result(out_off, why, out, n_slots):
+    """(out_off u64 [n_slots + 1], why u32 [n_slots], the replies u8 [out_off[-1]], or None when they did not fit
+    the `out` that was passed) from the outputs' bytes"""
+    off = out_off[: 8 * (n_slots + 1)].view(np.uint64)
+    total = int(off[-1])
+    return off, why[: 4 * n_slots].view(np.uint32), out[:total] if total <= out.size else None
+
+
+def relay_walked_cpu(records, buf, sess_off, slot_off, names=(), max_headers: int = 16, flags: int = 0,
+                     bytes_size: int | None = None, n_slots_total: int | None = None, out_size: int | None = None,
+                     date: bytes = DEFAULT_DATE):
+    """rhp_cpu_relay_walked (include/rhp_host.h) over `records`: (results, slots, msgs, hdrs) as a host walk
+    returned them (its first four), or crafted ones; buf the bytes that walk left (its fifth), sess_off, slot_off
+    and flags as it got them.  out_size None: the call runs twice, for the sizes and then with an `out` of exactly
+    their sum.  Returns (out_off, why, out) as _relay_result; all three held RELAY_POISON before the call."""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    ns = len(sess_off) - 1
+    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    res, slots, msgs, hdrs = (np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in records[:4])
+    text, nm, _ = classify_tables(names)
+    work = np.zeros(relay_work_words(nt), dtype=np.uint64)
+    w = WalkBatch(_ptr(buf), _ptr(buf), buf.size if bytes_size is None else bytes_size, _ptr(sess_off), _ptr(slot_off), ns,
+                  nt, max_headers, flags, _ptr(msgs) if msgs.size else None, _ptr(hdrs) if hdrs.size else None,
+                  _ptr(slots) if slots.size else None, _ptr(res) if res.size else None)
+
+    def run(size):
+        off = np.full(8 * (nt + 1), RELAY_POISON, dtype=np.uint8)
+        why = np.full(max(4 * nt, 1), RELAY_POISON, dtype=np.uint8)
+        out = np.full(size, RELAY_POISON, dtype=np.uint8)
+        r = WalkRelay(_ptr(text), _ptr(nm) if len(nm) else None, len(nm), len(date), date, _ptr(off), _ptr(why),
+                      _ptr(out) if size else None, size, _ptr(work))
+        rc = host().rhp_cpu_relay_walked(ctypes.byref(w), ctypes.byref(r))
+        if rc != 0:
+            raise RuntimeError(f"rhp_cpu_relay_walked failed: {rc}")
+        return off, why, out
+
+    if out_size is None:
+        out_size = int(run(0)[0].view(np.uint64)[-1])
+    return _relay_result(*run(out_size), nt)
+
+
+def relay_walked_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sessions: int, n_slots_total: int,
+                        max_headers: int, flags: int, msgs_t, hdrs_t, slots_t, results_t, names, out_off_t, why_t, out_t,
+                        out_size: int, work_t, date: bytes = DEFAULT_DATE, stream=None, steps: bool = False):
+    """One rhp_relay_walked call over device tensors on the stream (default: the current one): the batch as a
+    walk left it; out_off_t (8 * (n_slots_total + 1) bytes, 8-byte aligned), why_t (4 * n_slots_total bytes), out_t
+    (out_size bytes, any alignment; None with out_size 0) and work_t (8 * relay_work_words(n_slots_total) bytes).
+    Nothing is synchronised or copied (the names and the date travel in the launch).  steps: the measuring call
+    rhp_relay_walked_steps instead, which waits for the stream; returns (sizes, scan, copy) in microseconds."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    text, nm, _ = classify_tables(names)
+    w = WalkBatch(_addr(bytes_t), _addr(bytes_t), bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions,
+                  n_slots_total, max_headers, flags, _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+    r = WalkRelay(_ptr(text), _ptr(nm) if len(nm) else None, len(nm), len(date), date, _addr(out_off_t), _addr(why_t),
+                  _addr(out_t), out_size, _addr(work_t))
+    if steps:
+        us = (ctypes.c_float * 3)()
+        rc = lib().rhp_relay_walked_steps(ctypes.byref(w), ctypes.byref(r), ctypes.c_void_p(s.cuda_stream), ctypes.byref(us))
+    else:
+        rc = lib().rhp_relay_walked(ctypes.byref(w), ctypes.byref(r), ctypes.c_void_p(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_relay_walked failed: {rc}")
+    return tuple(us) if steps else None
+
+
+def relay_walked_gpu(buf, sess_off, slot_off, names=(), max_headers: int = 16, flags: int = 0, guard: int = 0,
+                     fill: int = RELAY_POISON, records=None, states=None, resume: bool = False, asked=None,
+                     bytes_size: int | None = None, n_slots_total: int | None = None, out_size: int | None = None,
+                     out_shift: int = 0, date: bytes = DEFAULT_DATE, steps: bool = False):
+    """The sessions walked and relayed on the GPU, on one stream, the walk's records left on the device between
+    the two.  The walk: rhp_walk_responses; with resume or states one round of rhp_walk_resume (states as
+    walk_resume_gpu takes them); with asked = (req_off, head_bits, n_req_total) rhp_walk_answers over that queue.
+    records: (results, slots, msgs, hdrs) copied in instead of walking (tests: crafted records).  out_size None:
+    the relay runs twice, for the sizes and then with an `out` of exactly their sum, `out_shift` bytes off a
+    512-byte boundary.  Every buffer is a Guarded device buffer (guard bytes on both sides, checked after the
+    calls); out_off, why and out hold `fill` first; steps: the call that writes the replies is rhp_relay_walked_steps;
+    replies that do not fit must leave out as it was.  Returns ((out_off, why, out) as relay_walked_cpu, what the
+    walk's *_gpu function returns up to the states)."""
+    import torch
+    buf = np.array(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    ns = len(sess_off) - 1
+    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    resume = resume or states is not None
+    size = buf.size if bytes_size is None else bytes_size
+    db = Guarded("bytes", buf.size, guard, data=buf)
+    gm = Guarded("msgs", max(16 * nt, 1), guard, fill=fill)
+    gh = Guarded("hdrs", max(8 * nt * max_headers, 1), guard, fill=fill)
+    gs = Guarded("slots", max(32 * nt, 1), guard, fill=fill)
+    gr = Guarded("results", max(16 * ns, 1), guard, fill=fill)
+    go = Guarded("out_off", 8 * (nt + 1), guard, fill=fill)
+    gy = Guarded("why", max(4 * nt, 4), guard, fill=fill)
+    gw = Guarded("work", 8 * relay_work_words(nt), guard, fill=fill)
+    extra = []
+    gt = None
+    if resume and records is None:
+        gt = states if isinstance(states, Guarded) else Guarded("states", max(32 * ns, 1), guard, data=_walk_states(states, ns))
+        extra.append(gt)
+    dso = torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda")
+    dsl = torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda")
+    batch = (db.view, size, dso, dsl, ns, nt, max_headers, flags, gm.view, gh.view, gs.view, gr.view)
+    if records is not None:
+        for g, a in zip((gr, gs, gm, gh), records[:4]):
+            a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            if a.size:
+                g.view[: a.size].copy_(torch.from_numpy(a.copy()))
+    elif asked is not None:
+        req_off, head_bits, nq = _walk_asked(*asked)
+        gq = Guarded("req_off", 4 * req_off.size, guard, data=req_off.view(np.uint8).copy())
+        gb = Guarded("head_bits", 4 * head_bits.size, guard, data=head_bits.view(np.uint8).copy())
+        ga = Guarded("answered", max(4 * ns, 4), guard, fill=fill)
+        extra += [gq, gb, ga]
+        walk_answers_device(*batch, gt.view if resume else None, gq.view, gb.view, nq, ga.view, None)
+    elif resume:
+        walk_resume_device(*batch, gt.view)
+    else:
+        walk_responses_device(*batch)
+
+    def run(n_out):
+        g = Guarded("out", max(n_out, 1), max(guard, 16) if out_shift else guard, fill=fill, shift=out_shift)
+        relay_walked_device(*batch, names, go.view, gy.view, g.view if n_out else None, n_out, gw.view, date, steps=steps and n_out > 0)
+        torch.cuda.synchronize()
+        return g
+
+    if out_size is None:
+        run(0)
+        out_size = int(go.view.cpu().numpy().view(np.uint64)[nt])
+        go.view.fill_(fill)
+        gy.view.fill_(fill)
+    gout = run(out_size)
+    if int(go.view.cpu().numpy().view(np.uint64)[nt]) > out_size:
+        assert bool((gout.view == (fill or 0)).all()), "the replies do not fit, and out was written"
+    if guard:
+        for g in [db, gm, gh, gs, gr, go, gy, gw, gout] + extra:
+            g.check()
+    out = _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
+                       db.view.cpu().numpy(), ns, nt, max_headers)
+    if gt is not None:
+        out += (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE), gt)
+    return _relay_result(go.view.cpu().numpy(), gy.view.cpu().numpy(), gout.view.cpu().numpy()[: max(out_size, 0)], nt), out

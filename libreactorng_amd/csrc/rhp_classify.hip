@@ -37,6 +37,14 @@
  * response walk (rhp_walk.hip) left: one slot per lane, the slot's session by
  * binary search over slot_off[], the head's first byte from slots[i].start,
  * the rules that let a slot through in rhp_lookup_args.h.
+ *
+ * rhp_relay_walked (rhp.h) re-writes the walked responses for the client side:
+ * http_write_response (src/reactor/http.c:236-297) for every slot that holds a
+ * whole response.  Its sizes step stands here because it is the lookup above
+ * with sixteen drop names in the same tables; its copy step is
+ * rhp_writer.hip's plan over the walked records, built from rhp_device.h's
+ * stage writers, and the scan between them is rhp_device.h's.  The rule is
+ * rhp_relay_args.h's.
  */
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -45,9 +53,11 @@
 
 #include "rhp.h"
 #include "rhp_classify_args.h"
+#define RHP_DEVICE_SCAN_KERNELS   /* this file launches rhp_device.h's two scan kernels */
 #include "rhp_device.h"
 #include "rhp_frame_args.h"
 #include "rhp_lookup_args.h"
+#include "rhp_relay_args.h"
 #include "rhp_scalar.h"
 
 namespace {
@@ -410,17 +420,19 @@ __global__ __launch_bounds__(256) void rhp_classify_sessions_kernel(SParams p)
   }
 }
 
+/* row j of the tables' names: the len bytes at s, folded to upper case */
+void pack_name(CTables &t, uint32_t j, const uint8_t *s, uint32_t len)
+{
+  uint8_t *d = reinterpret_cast<uint8_t *>(t.name[j]);
+  for (uint32_t q = 0; q < len; q++) d[q] = s[q] >= 'a' && s[q] <= 'z' ? (uint8_t) (s[q] - 0x20) : s[q];
+  t.name_len[j] = (uint8_t) len;
+}
+
 /* the caller's tables as the kernel's: names folded, route text packed */
 void pack_tables(const rhp_classify_t *c, CTables &t)
 {
   memset(&t, 0, sizeof t);
-  for (uint32_t j = 0; j < c->n_names; j++) {
-    const uint8_t *s = c->text + c->names[j].off;
-    const uint32_t len = c->names[j].len;
-    uint8_t *d = reinterpret_cast<uint8_t *>(t.name[j]);
-    for (uint32_t q = 0; q < len; q++) d[q] = s[q] >= 'a' && s[q] <= 'z' ? (uint8_t) (s[q] - 0x20) : s[q];
-    t.name_len[j] = (uint8_t) len;
-  }
+  for (uint32_t j = 0; j < c->n_names; j++) pack_name(t, j, c->text + c->names[j].off, c->names[j].len);
   uint32_t at = 0;   /* dwords of t.text in use */
   uint8_t *d = reinterpret_cast<uint8_t *>(t.text);
   for (uint32_t r = 0; r < c->n_routes; r++) {
@@ -694,7 +706,360 @@ __global__ __launch_bounds__(256) void rhp_lookup_walked_kernel(WParams p)
   for (uint32_t c = all & ~found; c; c &= c - 1u) p.fields[(uint64_t) __builtin_ctz(c) * n + i] = RHP_NAME_NULL;
 }
 
+/* ---- rhp_relay_walked ---- */
+
+/* the three names that are always dropped take the tables' last three rows and
+ * mask bits, the caller's the first RHP_RELAY_MAX_NAMES */
+constexpr uint32_t kTypeRow = RHP_RELAY_MAX_NAMES, kLengthRow = kTypeRow + 1u, kTeRow = kTypeRow + 2u;
+static_assert(kTeRow + 1u == RHP_CLASSIFY_MAX_NAMES, "sixteen rows, sixteen mask bits");
+
+struct RParams {
+  CTables         t;          /* first, as CParams */
+  const uint8_t  *bytes;
+  const uint64_t *sess_off, *slot_off;
+  uint64_t        head_readable, readable;   /* rhp_lookup_readable, rhp_relay_readable */
+  const uint4    *msgs;
+  const uint2    *hdrs;
+  const uint4    *slots;      /* two per slot */
+  const uint4    *results;
+  uint64_t       *out_off, *tile_sum, *plan;   /* plan: two words per slot */
+  uint32_t       *why;
+  uint32_t        n, m, flags, n_sessions;
+};
+static_assert(offsetof(RParams, t) == 0, "the tables lead the argument");
+static_assert(sizeof(RParams) <= 4096, "a kernel argument holds 4 KiB");
+static_assert(offsetof(rhp_walk_slot_t, body_len) == 8 && offsetof(rhp_walk_slot_t, wire_len) == 16 && offsetof(rhp_walk_slot_t, body_kind) == 28 &&
+              offsetof(rhp_walk_result_t, stop) == 4 && offsetof(rhp_msg_t, status) == 4 && offsetof(rhp_msg_t, msg_off) == 6 &&
+              offsetof(rhp_msg_t, msg_len) == 8, "records as 16-byte accesses");
+
+/* The sizes step: a tile of kTile slots per workgroup (the scan's tiles,
+ * rhp_device.h), a slot per lane and round.  rhp_lookup_walked_kernel's way to
+ * a head -- owner, in use, head, inside, and only then the records -- then the
+ * rule of rhp_relay_args.h: one pass over the head's rhp_hdr_t records that
+ * looks for an obs-fold line and a stray span and compares each name, by
+ * length first, with the sixteen rows.  It leaves why[i], the size in
+ * out_off[i + 1], the tile's sum, and for a relayed slot the plan the copy step
+ * reads: the kept records as a bit mask and the type's value. */
+__global__ __launch_bounds__(1024) void rhp_relay_sizes_kernel(RParams p)
+{
+  __shared__ uint32_t tab[kTabDwords];
+  __shared__ uint16_t lenmask[RHP_CLASSIFY_NAME_MAX + 1u];
+  __shared__ unsigned long long part[16];
+  {
+#if defined(__HIP_DEVICE_COMPILE__)   /* (as rhp_classify_kernel) */
+    const ka32 *ka = (const ka32 *) __builtin_amdgcn_kernarg_segment_ptr();
+#else
+    const ka32 *ka = nullptr;
+#endif
+    for (uint32_t t = threadIdx.x; t < kTabDwords; t += blockDim.x) tab[t] = ka[t];
+    if (threadIdx.x <= RHP_CLASSIFY_NAME_MAX) {
+      const ka32 *nl = ka + offsetof(CTables, name_len) / 4u;
+      uint32_t mk = 0;
+      for (uint32_t j = 0; j < RHP_CLASSIFY_MAX_NAMES; j++) {   /* (a row not in use has length 0) */
+        const uint32_t len = (nl[j >> 2] >> (8u * (j & 3u))) & 0xffu;
+        mk |= (len != 0u && len == threadIdx.x ? 1u : 0u) << j;
+      }
+      lenmask[threadIdx.x] = (uint16_t) mk;
+    }
+  }
+  __syncthreads();
+  const uint32_t *names = tab + offsetof(CTables, name) / 4u;
+  const uint32_t n = p.n, m = p.m;
+
+  unsigned long long sum = 0;
+  const uint64_t lo_i = (uint64_t) blockIdx.x * rhp_device::kTile, hi_i = min(lo_i + rhp_device::kTile, (uint64_t) n);
+  for (uint64_t i64 = lo_i + threadIdx.x; i64 < hi_i; i64 += 1024) {
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t above = rhp_lookup_sessions_upto(p.slot_off, p.n_sessions, i);
+    uint32_t why = RHP_RELAY_UNUSED;
+    uint64_t size = 0;
+    if (above) {
+      const uint32_t s = above - 1u;
+      const uint64_t lo = p.slot_off[s], hi = p.slot_off[s + 1u];
+      const uint4 res = p.results[s];
+      if (rhp_lookup_in_use(i, lo, hi, res.x, n)) {
+        const uint4 q = p.msgs[i], s0 = p.slots[2u * (uint64_t) i], s1 = p.slots[2u * (uint64_t) i + 1u];
+        const uint64_t st = (uint64_t) s0.x | (uint64_t) s0.y << 32, e = p.sess_off[s + 1u];
+        const int32_t ret = (int32_t) q.x;
+        why = rhp_relay_why_head(1, (int32_t) s1.z, ret, st, p.sess_off[s], e, p.head_readable, q.y & 0xffffu, (uint32_t) (i - lo), res.x, res.y);
+        if (why == RHP_RELAY_OK) {
+          const uint32_t msg_off = q.y >> 16, msg_len = q.z & 0xffffu;
+          uint32_t nh = q.w & 0xffffu;
+          if (nh > m) nh = m;   /* never more records than the batch holds */
+          bool fold = false, span_bad = msg_len != 0u && !rhp_relay_span_inside(msg_off, msg_len, ret), typed = false;
+          uint64_t keep = 0, fields = 0;
+          uint32_t type = 0;
+          for (uint32_t k = 0; k < nh; k++) {
+            const uint2 h = p.hdrs[(uint64_t) i * m + k];
+            const uint32_t noff = h.x & 0xffffu, nl = h.x >> 16, voff = h.y & 0xffffu, vl = h.y >> 16;
+            if (noff == RHP_NAME_NULL) { fold = true; continue; }   /* name == NULL: an obs-fold line */
+            if (!rhp_relay_span_inside(noff, nl, ret) || !rhp_relay_span_inside(voff, vl, ret)) { span_bad = true; continue; }
+            if (fold || span_bad) continue;
+            uint32_t cand = nl <= RHP_CLASSIFY_NAME_MAX ? (uint32_t) lenmask[nl] : 0u;
+            if (cand) cand = same_text<true>(p.bytes + st + noff, nl, cand, names, [](uint32_t j) { return j * kNameDwords; });
+            if ((cand >> kTypeRow & 1u) && !typed) {
+              typed = true;
+              type = h.y;
+            }
+            if (cand) continue;   /* dropped: every match, not only the first */
+            keep |= 1ull << k;
+            fields += rhp_relay_size_field(nl, vl);
+          }
+          const uint64_t body_len = (uint64_t) s0.z | (uint64_t) s0.w << 32, wire_len = (uint64_t) s1.x | (uint64_t) s1.y << 32;
+          why = rhp_relay_why_body(fold, span_bad, s1.w, body_len, wire_len, p.flags, st, ret, e, p.readable);
+          if (why == RHP_RELAY_OK) {
+            size = rhp_relay_size_head(msg_len, type >> 16, (uint32_t) body_len) + fields;
+            p.plan[2u * (uint64_t) i] = keep;
+            p.plan[2u * (uint64_t) i + 1u] = type;
+          }
+        }
+      }
+    }
+    p.why[i] = why;
+    p.out_off[i64 + 1u] = size;
+    sum += size;
+  }
+  rhp_device::block_sum_to(sum, part, &p.tile_sum[blockIdx.x]);
+}
+
+struct RWParams {
+  const uint8_t  *bytes;
+  const uint4    *msgs;
+  const uint2    *hdrs;
+  const uint4    *slots;
+  const uint64_t *out_off, *plan;
+  uint8_t        *out;
+  uint64_t        out_size;
+  uint32_t        n, m;
+  uint32_t        date[8];   /* the 29 date bytes, little-endian in dwords */
+};
+
+/* what the copy step needs of a relayed slot (one with a size): every span is
+ * inside the batch's bytes, the sizes step has seen to that */
+struct RelaySlot {
+  const uint8_t *head;
+  uint32_t ret, status, msg_off, msg_len, nh, type, body_len;
+  uint64_t keep;
+};
+__device__ __forceinline__ RelaySlot relay_slot(const RWParams &p, uint32_t i)
+{
+  const uint4 q = p.msgs[i], s0 = p.slots[2u * (uint64_t) i];
+  RelaySlot r;
+  r.head = p.bytes + ((uint64_t) s0.x | (uint64_t) s0.y << 32);
+  r.ret = q.x;
+  r.status = q.y & 0xffffu;
+  r.msg_off = q.y >> 16;
+  r.msg_len = q.z & 0xffffu;
+  r.nh = min(q.w & 0xffffu, p.m);
+  r.body_len = s0.z;   /* below 2^32 */
+  r.keep = p.plan[2u * (uint64_t) i];
+  r.type = (uint32_t) p.plan[2u * (uint64_t) i + 1u];
+  return r;
+}
+
+/* one reply, wave-cooperatively (the path for groups larger than the stage):
+ * rhp_writer.hip's write_one over a walked slot */
+__device__ void relay_one(const RWParams &p, uint32_t i, uint32_t lane)
+{
+  using rhp_device::put;
+  using rhp_device::put_const;
+  uint64_t o = p.out_off[i];
+  if (p.out_off[i + 1u] == o) return;   /* not relayed */
+  uint8_t *dst = p.out;
+  const RelaySlot r = relay_slot(p, i);
+  const auto span = [&](uint32_t off, uint32_t len) {
+    put(dst + o, r.head + off, len, lane);
+    o += len;
+  };
+  put_const(dst, o, "HTTP/1.1 ", lane);
+  if (lane < 3) dst[o + lane] = (uint8_t) ('0' + (lane == 0 ? r.status / 100u : lane == 1 ? r.status / 10u : r.status) % 10u);
+  o += 3;
+  if (r.msg_len) {
+    if (lane == 0) dst[o] = ' ';
+    o += 1;
+    span(r.msg_off, r.msg_len);
+  }
+  put_const(dst, o, "\r\nServer: *\r\nDate: ", lane);
+  if (lane < RHP_DATE_LEN) dst[o + lane] = (uint8_t) (p.date[lane >> 2] >> (8u * (lane & 3u)));
+  o += RHP_DATE_LEN;
+  put_const(dst, o, "\r\nContent-Type: ", lane);
+  span(r.type & 0xffffu, r.type >> 16);
+  put_const(dst, o, "\r\nContent-Length: ", lane);
+  const uint32_t D = rhp_u32_len(r.body_len);   /* http_u32_sprint: most significant first */
+  if (lane < D) {
+    uint32_t x = r.body_len;
+    for (uint32_t q = D - 1u; q > lane; q--) x /= 10u;
+    dst[o + lane] = (uint8_t) ('0' + x % 10u);
+  }
+  o += D;
+  put_const(dst, o, "\r\n", lane);
+  for (uint64_t c = r.keep; c; c &= c - 1u) {   /* http_push_field (http.c:61-69) */
+    const uint32_t k = (uint32_t) __builtin_ctzll(c);
+    if (k >= r.nh) break;
+    const uint2 h = p.hdrs[(uint64_t) i * p.m + k];
+    span(h.x & 0xffffu, h.x >> 16);
+    put_const(dst, o, ": ", lane);
+    span(h.y & 0xffffu, h.y >> 16);
+    put_const(dst, o, "\r\n", lane);
+  }
+  put_const(dst, o, "\r\n", lane);   /* the empty line */
+  span(r.ret, r.body_len);
+}
+
+constexpr uint32_t kRelayStage = 16384;   /* LDS bytes per wave, as rhp_writer.hip's: groups up to 16 KiB - 16 */
+
+/* The copy step, rhp_resp_write_kernel's plan over the walked slots: a wave per
+ * 64 consecutive slots; each lane assembles its slot's reply, if it has one, in
+ * the wave's LDS stage in the reference's push order, then the wave stores the
+ * group's contiguous output with 16-byte stores (flush_stage, rhp_device.h).  A
+ * group larger than the stage is written reply by reply, the wave's 64 lanes
+ * copying each segment. */
+__global__ __launch_bounds__(256) void rhp_relay_write_kernel(RWParams p)
+{
+  using namespace rhp_device;
+  __shared__ __attribute__((aligned(16))) uint8_t stage_all[4 * kRelayStage];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+  if (p.out_off[p.n] > p.out_size) return;   /* does not fit: sizes only (rhp.h) */
+  lds8 *L = (lds8 *) (stage_all + wv * kRelayStage);
+  const uint32_t groups = (p.n + 63u) / 64u;
+  for (uint32_t g = wave; g < groups; g += nwaves) {
+    const uint32_t i0 = g * 64u, i1 = min(i0 + 64u, p.n);
+    const uint64_t G0 = p.out_off[i0], G1 = p.out_off[i1];
+    if (G0 == G1) continue;   /* no slot of the group is relayed */
+    const uint32_t shift = (uint32_t) (uintptr_t) (p.out + G0) & 15u;   /* LDS and HBM agree modulo 16 */
+    if (G1 - G0 + shift > kRelayStage) {   /* big replies: the cooperative path */
+      for (uint32_t i = i0; i < i1; i++) relay_one(p, i, lane);
+      continue;
+    }
+    const uint32_t i = i0 + lane;
+    if (i < i1) {
+      const uint64_t at = p.out_off[i];
+      if (p.out_off[i + 1u] != at) {
+        const RelaySlot r = relay_slot(p, i);
+        uint32_t o = shift + (uint32_t) (at - G0);
+        st_const(L, o, "HTTP/1.1 ");
+        L[o] = (uint8_t) ('0' + r.status / 100u % 10u);
+        L[o + 1] = (uint8_t) ('0' + r.status / 10u % 10u);
+        L[o + 2] = (uint8_t) ('0' + r.status % 10u);
+        o += 3;
+        if (r.msg_len) {
+          L[o++] = ' ';
+          st_span(L, o, r.head + r.msg_off, r.msg_len);
+        }
+        st_const(L, o, "\r\nServer: *\r\nDate: ");
+#pragma unroll
+        for (uint32_t j = 0; j < RHP_DATE_LEN; j++) L[o + j] = (uint8_t) (p.date[j >> 2] >> (8u * (j & 3u)));
+        o += RHP_DATE_LEN;
+        st_const(L, o, "\r\nContent-Type: ");
+        st_span(L, o, r.head + (r.type & 0xffffu), r.type >> 16);
+        st_const(L, o, "\r\nContent-Length: ");
+        const uint32_t D = rhp_u32_len(r.body_len);   /* http_u32_sprint: most significant first */
+        for (uint32_t j = D, x = r.body_len; j-- > 0; x /= 10u) L[o + j] = (uint8_t) ('0' + x % 10u);
+        o += D;
+        st_const(L, o, "\r\n");
+        for (uint64_t c = r.keep; c; c &= c - 1u) {   /* http_push_field (http.c:61-69) */
+          const uint32_t k = (uint32_t) __builtin_ctzll(c);
+          if (k >= r.nh) break;
+          const uint2 h = p.hdrs[(uint64_t) i * p.m + k];
+          st_span(L, o, r.head + (h.x & 0xffffu), h.x >> 16);
+          st_const(L, o, ": ");
+          st_span(L, o, r.head + (h.y & 0xffffu), h.y >> 16);
+          st_const(L, o, "\r\n");
+        }
+        st_const(L, o, "\r\n");   /* the empty line */
+        st_span(L, o, r.head + r.ret, r.body_len);
+      }
+    }
+    flush_stage(L, shift, p.out, G0, G1, lane);
+  }
+}
+
 }  // namespace
+
+/* the call; ev: NULL, or four events recorded before the sizes step, behind it,
+ * behind the two scan kernels and behind the copy step (rhp_relay_walked_steps) */
+static int relay_launch(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r, hipStream_t s, hipEvent_t *ev)
+{
+  const int rc = rhp_relay_check(w, r, 1);
+  if (rc < 0) return rc;
+  if (rc != 0) {   /* no slot: out_off[0] = 0, one 8-byte memset node and no kernel */
+    if (ev) return -22;
+    return (int) hipMemsetAsync(r->out_off, 0, sizeof(uint64_t), s);
+  }
+  const uint32_t n = w->n_slots_total, tiles = (n + rhp_device::kTile - 1u) / rhp_device::kTile;
+  RParams p;
+  const rhp_classify_t names = {r->text, r->names, nullptr, r->n_names, 0, nullptr, nullptr};
+  pack_tables(&names, p.t);
+  const char *const builtin[3] = {RHP_RELAY_TYPE_NAME, RHP_RELAY_LENGTH_NAME, RHP_RELAY_TE_NAME};   /* rows kTypeRow.. */
+  for (uint32_t j = 0; j < 3u; j++) pack_name(p.t, kTypeRow + j, (const uint8_t *) builtin[j], (uint32_t) strlen(builtin[j]));
+  p.bytes = w->bytes;
+  p.sess_off = w->sess_off;
+  p.slot_off = w->slot_off;
+  p.head_readable = rhp_lookup_readable(w->bytes_size);
+  p.readable = rhp_relay_readable(w->bytes_size);
+  p.msgs = reinterpret_cast<const uint4 *>(w->msgs);
+  p.hdrs = reinterpret_cast<const uint2 *>(w->hdrs);
+  p.slots = reinterpret_cast<const uint4 *>(w->slots);
+  p.results = reinterpret_cast<const uint4 *>(w->results);
+  p.out_off = r->out_off;
+  p.tile_sum = r->work;
+  p.plan = r->work + tiles + 1u;
+  p.why = r->why;
+  p.n = n;
+  p.m = w->max_headers;
+  p.flags = w->flags;
+  p.n_sessions = w->n_sessions;
+  RWParams q;
+  q.bytes = w->bytes;
+  q.msgs = p.msgs;
+  q.hdrs = p.hdrs;
+  q.slots = p.slots;
+  q.out_off = r->out_off;
+  q.plan = p.plan;
+  q.out = r->out;
+  q.out_size = r->out_size;
+  q.n = n;
+  q.m = w->max_headers;
+  memset(q.date, 0, sizeof q.date);
+  memcpy(q.date, r->date, RHP_DATE_LEN);
+  if (ev) (void) hipEventRecord(ev[0], s);
+  hipLaunchKernelGGL(rhp_relay_sizes_kernel, dim3(tiles), dim3(1024), 0, s, p);
+  if (ev) (void) hipEventRecord(ev[1], s);
+  hipLaunchKernelGGL(rhp_device::rhp_resp_top_scan_kernel, dim3(1), dim3(1024), 0, s, r->work, tiles);
+  hipLaunchKernelGGL(rhp_device::rhp_resp_tile_scan_kernel, dim3(tiles), dim3(1024), 0, s, r->out_off, n, (const uint64_t *) r->work);
+  if (ev) (void) hipEventRecord(ev[2], s);
+  /* 4 waves per workgroup, a wave per 64 slots */
+  hipLaunchKernelGGL(rhp_relay_write_kernel, dim3((uint32_t) (((uint64_t) n + 255u) / 256u)), dim3(256), 0, s, q);
+  if (ev) (void) hipEventRecord(ev[3], s);
+  return (int) hipGetLastError();
+}
+
+extern "C" int rhp_relay_walked(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r, void *stream)
+{
+  return relay_launch(w, r, reinterpret_cast<hipStream_t>(stream), nullptr);
+}
+
+/* the call with a HIP event between its steps, for measuring (rhp.h): it
+ * creates and destroys its events and waits for the stream */
+extern "C" int rhp_relay_walked_steps(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r, void *stream, float us[3])
+{
+  if (!us) return -22;
+  int rc = rhp_relay_check(w, r, 1);   /* (the refusals come before anything is created) */
+  if (rc != 0) return -22;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < 4 && rc == 0; k++) rc = (int) hipEventCreate(&ev[k]);
+  if (rc == 0) rc = relay_launch(w, r, reinterpret_cast<hipStream_t>(stream), ev);
+  if (rc == 0) rc = (int) hipEventSynchronize(ev[3]);
+  for (int k = 0; k < 3 && rc == 0; k++) {
+    float ms = 0;
+    rc = (int) hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+    us[k] = ms * 1e3f;
+  }
+  for (int k = 0; k < 4; k++)
+    if (ev[k]) (void) hipEventDestroy(ev[k]);
+  return rc;
+}
 
 extern "C" int rhp_classify_batch(const rhp_batch_t *b, const rhp_classify_t *c, void *stream)
 {

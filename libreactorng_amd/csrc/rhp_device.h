@@ -34,6 +34,123 @@ __device__ __forceinline__ T wave_incl_scan(T v, uint32_t lane)
   return v;
 }
 
+/* out_off[1..n] sizes -> out_off[0..n] offsets, reduce-then-scan over tiles of
+ * kTile sizes: tile sums into work[], one workgroup scans work[] (exclusive),
+ * then every tile is scanned in place with its carry.  Loads and stores are
+ * coalesced; within a workgroup a thread scans 4 consecutive sizes, a wave its
+ * 64 threads through shuffles, the workgroup its 16 waves through LDS.
+ * (rhp_writer.hip and rhp_classify.hip's relay: each writes the sizes and the
+ * tile sums in a kernel of its own and launches the two kernels below.) */
+constexpr uint32_t kTile = 4096;   /* 1024 threads x 4 */
+
+/* inclusive scan of one value per thread over a 1024-thread workgroup */
+__device__ __forceinline__ unsigned long long block_incl_scan(unsigned long long v, unsigned long long *part)
+{
+  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+  v = wave_incl_scan(v, lane);
+  if (lane == 63) part[w] = v;
+  __syncthreads();
+  if (w == 0) {
+    unsigned long long x = lane < 16 ? part[lane] : 0;
+    x = wave_incl_scan(x, lane);
+    if (lane < 16) part[lane] = x;
+  }
+  __syncthreads();
+  return v + (w ? part[w - 1] : 0);
+}
+
+/* a tile's sum from one partial sum per thread of a 1024-thread workgroup */
+__device__ __forceinline__ void block_sum_to(unsigned long long s, unsigned long long *part, uint64_t *to)
+{
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < 16; w++) t += part[w];
+    *to = t;
+  }
+}
+
+/* The two scan kernels, only in a file that defines RHP_DEVICE_SCAN_KERNELS before
+ * it includes this header (rhp_writer.hip, rhp_classify.hip): every other file
+ * would emit and register kernels it never launches. */
+#if defined(RHP_DEVICE_SCAN_KERNELS)
+/* work[0..tiles) -> exclusive offsets (one workgroup, 1024 per round) */
+static __global__ __launch_bounds__(1024) void rhp_resp_top_scan_kernel(uint64_t *work, uint32_t tiles)
+{
+  __shared__ unsigned long long part[16];
+  unsigned long long carry = 0;
+  for (uint32_t b = 0; b < tiles; b += 1024) {
+    const uint32_t k = b + threadIdx.x;
+    const unsigned long long v = k < tiles ? work[k] : 0;
+    const unsigned long long inc = block_incl_scan(v, part);
+    if (k < tiles) work[k] = carry + inc - v;
+    carry += part[15];   /* the round's total */
+    __syncthreads();
+  }
+}
+
+static __global__ __launch_bounds__(1024) void rhp_resp_tile_scan_kernel(uint64_t *a, uint32_t n, const uint64_t *work)
+{
+  __shared__ unsigned long long part[16];
+  const uint64_t base = 1 + (uint64_t) blockIdx.x * kTile + 4u * threadIdx.x, end = (uint64_t) n + 1;
+  unsigned long long x[4], s = 0;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    x[q] = base + q < end ? a[base + q] : 0;
+    s += x[q];
+    x[q] = s;   /* thread-local inclusive */
+  }
+  const unsigned long long before = block_incl_scan(s, part) - s + work[blockIdx.x];
+#pragma unroll
+  for (int q = 0; q < 4; q++)
+    if (base + q < end) a[base + q] = before + x[q];
+  if (blockIdx.x == 0 && threadIdx.x == 0) a[0] = 0;
+}
+
+#endif
+
+/* ---- the lane-per-reply stage writers (LDS byte o of the wave's stage) ---- */
+/* a compile-time constant string */
+template <uint32_t N>
+__device__ __forceinline__ void st_const(lds8 *L, uint32_t &o, const char (&s)[N])
+{
+#pragma unroll
+  for (uint32_t j = 0; j + 1 < N; j++) L[o + j] = (uint8_t) s[j];
+  o += N - 1;
+}
+/* len bytes from global memory at src: the aligned dwords that hold them (no
+ * byte outside [src & ~3, src + len + 3) is read), funnel-shifted */
+__device__ __forceinline__ void st_span(lds8 *L, uint32_t &o, const uint8_t *src, uint32_t len)
+{
+  const uintptr_t a = (uintptr_t) src;
+  const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t) 3);
+  const uint32_t sh = (uint32_t) a & 3u, nd = (sh + len + 3u) >> 2;
+  uint32_t lo = len ? w[0] : 0;
+  for (uint32_t j = 0; j < len; j += 4) {
+    const uint32_t k = (j >> 2) + 1u;
+    const uint32_t hi = k < nd ? w[k] : 0u;
+    const uint32_t d = __builtin_amdgcn_alignbyte(hi, lo, sh);
+    L[o + j] = (uint8_t) d;
+    if (j + 1 < len) L[o + j + 1] = (uint8_t) (d >> 8);
+    if (j + 2 < len) L[o + j + 2] = (uint8_t) (d >> 16);
+    if (j + 3 < len) L[o + j + 3] = (uint8_t) (d >> 24);
+    lo = hi;
+  }
+  o += len;
+}
+
+/* a compile-time constant string across the wave (shorter than 64 bytes), o
+ * advancing past it: the cooperative twin of st_const */
+template <uint32_t N>
+__device__ __forceinline__ void put_const(uint8_t *dst, uint64_t &o, const char (&s)[N], uint32_t lane)
+{
+  static_assert(N - 1 <= 64, "a byte per lane");
+  if (lane < N - 1) dst[o + lane] = (uint8_t) s[lane];
+  o += N - 1;
+}
+
 /* d[0, len) <- src[0, len) across the wave, all 64 lanes calling: bytes up to
  * the first 16-aligned destination, then 16 bytes per lane (1 KiB per store
  * instruction) from funnel-shifted aligned source dwords, then the tail bytes;

@@ -2,7 +2,7 @@
  * rhp_host.cpp -- the product's host entry points (rhp_host.h): the exact
  * scalar parser over a batch in host memory, the session fix-up, the dense
  * pack and the three expansions, the host classify, reply, gather and split, the
- * message parse (responses, header blocks), their framing, the chunked decoder, the response walk, and the pointer-based
+ * message parse (responses, header blocks), their framing, the chunked decoder, the response walk, its lookup and its relay, and the pointer-based
  * rhp_phr_parse_request / _response / _headers, rhp_phr_decode_chunked and rhp_http_read_cpu.  libreactor.so links them.  The
  * parser is rhp_scalar.h's (the code the kernel's rare paths run); where the
  * records sit and how they are encoded is rhp_records.h's.
@@ -24,6 +24,7 @@
 #include "rhp_frame_args.h"
 #include "rhp_walk_args.h"
 #include "rhp_lookup_args.h"
+#include "rhp_relay_args.h"
 #include "rhp_host_exact.h"
 
 using namespace rhp;
@@ -668,6 +669,128 @@ extern "C" int rhp_cpu_lookup_walked(const rhp_walk_batch_t *w, const rhp_walk_l
     r.ret = ret;
     r.num_headers = w->msgs[i].num_headers;
     classify_one(&c, n, m, i, w->bytes + st, r, [&](uint32_t k) -> const rhp_hdr_t & { return w->hdrs[(size_t) i * m + k]; });
+  }
+  return 0;
+}
+
+/* rhp_relay_walked (rhp.h) on the host, every pointer in host memory: slot by
+ * slot the rule of rhp_relay_args.h (the kernels' own: the owner by the same
+ * bisection, the tests in rhp.h's order, the sizes), then, when everything
+ * fits, every relayed slot's reply in http_write_response's push order, a byte
+ * at a time.  It shares the argument check with the launcher. */
+namespace {
+
+struct RelayPlan {
+  uint32_t why;
+  uint64_t size, keep;      /* keep: bit k set: header record k is a field of the reply */
+  uint32_t type_off, type_len;
+};
+
+bool relay_same_name(const uint8_t *s, uint32_t len, const uint8_t *name, uint32_t name_len)
+{
+  const auto upper = [](uint8_t x) { return x >= 'a' && x <= 'z' ? (uint8_t) (x - ('a' - 'A')) : x; };   /* C-locale toupper */
+  if (len != name_len) return false;
+  for (uint32_t q = 0; q < len; q++)
+    if (upper(s[q]) != upper(name[q])) return false;
+  return true;
+}
+
+RelayPlan relay_plan(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r, uint32_t i, uint64_t head_readable, uint64_t readable)
+{
+  RelayPlan p = {RHP_RELAY_UNUSED, 0, 0, 0, 0};
+  const uint32_t n = w->n_slots_total, m = w->max_headers;
+  const uint32_t above = rhp_lookup_sessions_upto(w->slot_off, w->n_sessions, i);
+  if (!above) return p;
+  const uint32_t s = above - 1u;
+  const uint64_t lo = w->slot_off[s];
+  if (!rhp_lookup_in_use(i, lo, w->slot_off[s + 1], w->results[s].n_slots, n)) return p;
+  const rhp_msg_t &g = w->msgs[i];
+  const rhp_walk_slot_t &t = w->slots[i];
+  const uint64_t e = w->sess_off[s + 1];
+  p.why = rhp_relay_why_head(1, t.result, g.ret, t.start, w->sess_off[s], e, head_readable, g.status, (uint32_t) (i - lo),
+                             w->results[s].n_slots, w->results[s].stop);
+  if (p.why != RHP_RELAY_OK) return p;
+  const uint8_t *head = w->bytes + t.start;
+  const uint32_t nh = g.num_headers < m ? g.num_headers : m;
+  bool fold = false, span_bad = g.msg_len > 0 && !rhp_relay_span_inside(g.msg_off, g.msg_len, g.ret), typed = false;
+  uint64_t fields = 0;
+  for (uint32_t k = 0; k < nh; k++) {
+    const rhp_hdr_t &h = w->hdrs[(size_t) i * m + k];
+    if (h.name_off == RHP_NAME_NULL) { fold = true; continue; }
+    if (!rhp_relay_span_inside(h.name_off, h.name_len, g.ret) || !rhp_relay_span_inside(h.value_off, h.value_len, g.ret)) { span_bad = true; continue; }
+    if (fold || span_bad) continue;
+    const uint8_t *name = head + h.name_off;
+    bool drop = false;
+    if (relay_same_name(name, h.name_len, (const uint8_t *) RHP_RELAY_TYPE_NAME, sizeof RHP_RELAY_TYPE_NAME - 1)) {
+      drop = true;
+      if (!typed) { typed = true; p.type_off = h.value_off; p.type_len = h.value_len; }
+    }
+    drop = drop || relay_same_name(name, h.name_len, (const uint8_t *) RHP_RELAY_LENGTH_NAME, sizeof RHP_RELAY_LENGTH_NAME - 1) ||
+           relay_same_name(name, h.name_len, (const uint8_t *) RHP_RELAY_TE_NAME, sizeof RHP_RELAY_TE_NAME - 1);
+    for (uint32_t j = 0; j < r->n_names && !drop; j++) drop = relay_same_name(name, h.name_len, r->text + r->names[j].off, r->names[j].len);
+    if (drop) continue;
+    p.keep |= 1ull << k;
+    fields += rhp_relay_size_field(h.name_len, h.value_len);
+  }
+  p.why = rhp_relay_why_body(fold, span_bad, t.body_kind, t.body_len, t.wire_len, w->flags, t.start, g.ret, e, readable);
+  if (p.why == RHP_RELAY_OK) p.size = rhp_relay_size_head(g.msg_len, p.type_len, (uint32_t) t.body_len) + fields;
+  return p;
+}
+
+/* http_write_response's pushes (http.c:236-284) for slot i at d; returns the end */
+uint8_t *relay_write(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r, uint32_t i, const RelayPlan &p, uint8_t *d)
+{
+  const rhp_msg_t &g = w->msgs[i];
+  const rhp_walk_slot_t &t = w->slots[i];
+  const uint8_t *head = w->bytes + t.start;
+  const auto text = [&](const char *s) { const size_t l = strlen(s); memcpy(d, s, l); d += l; };
+  const auto span = [&](const uint8_t *s, size_t l) { if (l) memcpy(d, s, l); d += l; };
+  text("HTTP/1.1 ");
+  *d++ = (uint8_t) ('0' + g.status / 100u % 10u); *d++ = (uint8_t) ('0' + g.status / 10u % 10u); *d++ = (uint8_t) ('0' + g.status % 10u);
+  if (g.msg_len) { *d++ = ' '; span(head + g.msg_off, g.msg_len); }
+  text("\r\nServer: *\r\nDate: ");
+  span((const uint8_t *) r->date, RHP_DATE_LEN);
+  text("\r\nContent-Type: ");
+  span(head + p.type_off, p.type_len);
+  text("\r\nContent-Length: ");
+  const uint32_t v = (uint32_t) t.body_len, L = rhp_u32_len(v);
+  for (uint32_t q = 0, x = v; q < L; q++, x /= 10u) d[L - 1u - q] = (uint8_t) ('0' + x % 10u);   /* http_u32_sprint */
+  d += L;
+  text("\r\n");
+  const uint32_t m = w->max_headers, nh = g.num_headers < m ? g.num_headers : m;
+  for (uint32_t k = 0; k < nh; k++) {
+    if (!(p.keep >> k & 1u)) continue;
+    const rhp_hdr_t &h = w->hdrs[(size_t) i * m + k];
+    span(head + h.name_off, h.name_len); text(": "); span(head + h.value_off, h.value_len); text("\r\n");
+  }
+  text("\r\n");
+  span(head + (uint32_t) g.ret, (size_t) t.body_len);
+  return d;
+}
+
+}  // namespace
+
+extern "C" int rhp_cpu_relay_walked(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r)
+{
+  const int rc = rhp_relay_check(w, r, 0);
+  if (rc < 0) return rc;
+  uint64_t zero = 0;
+  memcpy(r->out_off, &zero, sizeof zero);   /* (any alignment) */
+  if (rc != 0) return 0;
+  const uint32_t n = w->n_slots_total;
+  const uint64_t head_readable = rhp_lookup_readable(w->bytes_size), readable = rhp_relay_readable(w->bytes_size);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const RelayPlan p = relay_plan(w, r, i, head_readable, readable);
+    total += p.size;
+    memcpy((uint8_t *) r->why + 4u * (size_t) i, &p.why, 4);
+    memcpy((uint8_t *) r->out_off + 8u * ((size_t) i + 1u), &total, 8);
+  }
+  if (total > r->out_size) return 0;
+  uint8_t *d = r->out;
+  for (uint32_t i = 0; i < n; i++) {
+    const RelayPlan p = relay_plan(w, r, i, head_readable, readable);
+    if (p.why == RHP_RELAY_OK) d = relay_write(w, r, i, p, d);
   }
   return 0;
 }

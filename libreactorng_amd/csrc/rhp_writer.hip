@@ -35,6 +35,7 @@
 #include <string.h>
 
 #include "rhp.h"
+#define RHP_DEVICE_SCAN_KERNELS   /* this file launches rhp_device.h's two scan kernels */
 #include "rhp_device.h"
 
 namespace {
@@ -83,28 +84,8 @@ __device__ __forceinline__ uint64_t resp_size(const WParams &p, const rhp_resp_t
 }
 
 
-/* out_off[1..n] sizes -> out_off[0..n] offsets, reduce-then-scan over tiles of
- * kTile sizes: tile sums into work[], one workgroup scans work[] (exclusive),
- * then every tile is scanned in place with its carry.  Loads and stores are
- * coalesced; within a workgroup a thread scans 4 consecutive sizes, a wave its
- * 64 threads through shuffles, the workgroup its 16 waves through LDS. */
-constexpr uint32_t kTile = 4096;   /* 1024 threads x 4 */
-
-/* inclusive scan of one value per thread over a 1024-thread workgroup */
-__device__ __forceinline__ unsigned long long block_incl_scan(unsigned long long v, unsigned long long *part)
-{
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  v = wave_incl_scan(v, lane);
-  if (lane == 63) part[w] = v;
-  __syncthreads();
-  if (w == 0) {
-    unsigned long long x = lane < 16 ? part[lane] : 0;
-    x = wave_incl_scan(x, lane);
-    if (lane < 16) part[lane] = x;
-  }
-  __syncthreads();
-  return v + (w ? part[w - 1] : 0);
-}
+/* the reduce-then-scan over tiles of kTile sizes (kTile, block_incl_scan and the
+ * two scan kernels) is rhp_device.h's, shared with rhp_classify.hip's relay */
 
 /* sizes of a tile's responses into out_off[1..], and the tile's sum */
 __global__ __launch_bounds__(1024) void rhp_resp_tile_sum_kernel(WParams p, uint64_t *work)
@@ -117,47 +98,7 @@ __global__ __launch_bounds__(1024) void rhp_resp_tile_sum_kernel(WParams p, uint
     p.out_off[k] = z;
     s += z;
   }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int w = 0; w < 16; w++) t += part[w];
-    work[blockIdx.x] = t;
-  }
-}
-
-/* work[0..tiles) -> exclusive offsets (one workgroup, 1024 per round) */
-__global__ __launch_bounds__(1024) void rhp_resp_top_scan_kernel(uint64_t *work, uint32_t tiles)
-{
-  __shared__ unsigned long long part[16];
-  unsigned long long carry = 0;
-  for (uint32_t b = 0; b < tiles; b += 1024) {
-    const uint32_t k = b + threadIdx.x;
-    const unsigned long long v = k < tiles ? work[k] : 0;
-    const unsigned long long inc = block_incl_scan(v, part);
-    if (k < tiles) work[k] = carry + inc - v;
-    carry += part[15];   /* the round's total */
-    __syncthreads();
-  }
-}
-
-__global__ __launch_bounds__(1024) void rhp_resp_tile_scan_kernel(uint64_t *a, uint32_t n, const uint64_t *work)
-{
-  __shared__ unsigned long long part[16];
-  const uint64_t base = 1 + (uint64_t) blockIdx.x * kTile + 4u * threadIdx.x, end = (uint64_t) n + 1;
-  unsigned long long x[4], s = 0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    x[q] = base + q < end ? a[base + q] : 0;
-    s += x[q];
-    x[q] = s;   /* thread-local inclusive */
-  }
-  const unsigned long long before = block_incl_scan(s, part) - s + work[blockIdx.x];
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-    if (base + q < end) a[base + q] = before + x[q];
-  if (blockIdx.x == 0 && threadIdx.x == 0) a[0] = 0;
+  block_sum_to(s, part, &work[blockIdx.x]);
 }
 
 /* one segment of a response across the wave (rhp_device.h), o advancing past it */
@@ -202,36 +143,7 @@ __device__ void write_one(const WParams &p, uint32_t i, uint32_t lane)
   put(dst, o, p.arena + r.body.off, r.body.len, lane);
 }
 
-/* ---- the lane-per-response stage writers (LDS byte o of the wave's stage) ---- */
-/* a compile-time constant string */
-template <uint32_t N>
-__device__ __forceinline__ void st_const(lds8 *L, uint32_t &o, const char (&s)[N])
-{
-#pragma unroll
-  for (uint32_t j = 0; j + 1 < N; j++) L[o + j] = (uint8_t) s[j];
-  o += N - 1;
-}
-/* len bytes from global memory at src: the aligned dwords that hold them (no
- * byte outside [src & ~3, src + len + 3) is read), funnel-shifted */
-__device__ __forceinline__ void st_span(lds8 *L, uint32_t &o, const uint8_t *src, uint32_t len)
-{
-  const uintptr_t a = (uintptr_t) src;
-  const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t) 3);
-  const uint32_t sh = (uint32_t) a & 3u, nd = (sh + len + 3u) >> 2;
-  uint32_t lo = len ? w[0] : 0;
-  for (uint32_t j = 0; j < len; j += 4) {
-    const uint32_t k = (j >> 2) + 1u;
-    const uint32_t hi = k < nd ? w[k] : 0u;
-    const uint32_t d = __builtin_amdgcn_alignbyte(hi, lo, sh);
-    L[o + j] = (uint8_t) d;
-    if (j + 1 < len) L[o + j + 1] = (uint8_t) (d >> 8);
-    if (j + 2 < len) L[o + j + 2] = (uint8_t) (d >> 16);
-    if (j + 3 < len) L[o + j + 3] = (uint8_t) (d >> 24);
-    lo = hi;
-  }
-  o += len;
-}
-
+/* the lane-per-response stage writers (st_const, st_span) are rhp_device.h's */
 constexpr uint32_t kStage = 16384;   /* LDS bytes per wave: groups up to 16 KiB - 16 */
 
 __global__ __launch_bounds__(256) void rhp_resp_write_kernel(WParams p)
@@ -287,13 +199,21 @@ std::atomic<int> g_writer_cus[kWriterMaxDevices];
 
 }  // namespace
 
-extern "C" int rhp_write_responses(const rhp_resp_batch_t *b, void *stream)
+/* the call; ev: NULL, or four events recorded before the sizes step, behind it,
+ * behind the two scan kernels and behind the copy step (rhp_write_responses_steps) */
+static int write_check(const rhp_resp_batch_t *b)
 {
   if (!b) return -22;
   if (!b->out_off || !b->date || b->date_len != RHP_DATE_LEN) return -22;
   if (b->n > 0 && (!b->arena || !b->resps)) return -22;
   if (!b->out && b->out_size != 0) return -22;
   if (b->n > 0 && !b->work) return -22;
+  return 0;
+}
+
+static int write_launch(const rhp_resp_batch_t *b, void *stream, hipEvent_t *ev)
+{
+  if (write_check(b) != 0) return -22;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int dev = 0, cus = 0;
   {
@@ -317,15 +237,41 @@ extern "C" int rhp_write_responses(const rhp_resp_batch_t *b, void *stream)
   p.n = b->n;
   memset(p.date, 0, sizeof p.date);
   memcpy(p.date, b->date, RHP_DATE_LEN);
-  if (b->n == 0) return (int) hipMemsetAsync(b->out_off, 0, sizeof(uint64_t), s);
+  if (b->n == 0) return ev ? -22 : (int) hipMemsetAsync(b->out_off, 0, sizeof(uint64_t), s);
   const uint32_t cap = (uint32_t) cus * 8u;
   const uint32_t tiles = (b->n + kTile - 1u) / kTile;
+  if (ev) (void) hipEventRecord(ev[0], s);
   hipLaunchKernelGGL(rhp_resp_tile_sum_kernel, dim3(tiles), dim3(1024), 0, s, p, b->work);
+  if (ev) (void) hipEventRecord(ev[1], s);
   hipLaunchKernelGGL(rhp_resp_top_scan_kernel, dim3(1), dim3(1024), 0, s, b->work, tiles);
   hipLaunchKernelGGL(rhp_resp_tile_scan_kernel, dim3(tiles), dim3(1024), 0, s, b->out_off, b->n,
                      (const uint64_t *) b->work);
+  if (ev) (void) hipEventRecord(ev[2], s);
   uint32_t g3 = (b->n + 255u) / 256u;   /* 4 waves per workgroup, a wave per 64 responses */
   if (g3 > cap) g3 = cap;
   hipLaunchKernelGGL(rhp_resp_write_kernel, dim3(g3), dim3(256), 0, s, p);
+  if (ev) (void) hipEventRecord(ev[3], s);
   return (int) hipGetLastError();
+}
+
+extern "C" int rhp_write_responses(const rhp_resp_batch_t *b, void *stream) { return write_launch(b, stream, nullptr); }
+
+/* the call with a HIP event between its steps, for measuring (rhp.h): it
+ * creates and destroys its events and waits for the stream */
+extern "C" int rhp_write_responses_steps(const rhp_resp_batch_t *b, void *stream, float us[3])
+{
+  if (!us || write_check(b) != 0 || b->n == 0) return -22;   /* (the refusals come before anything is created) */
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  int rc = 0;
+  for (int k = 0; k < 4 && rc == 0; k++) rc = (int) hipEventCreate(&ev[k]);
+  if (rc == 0) rc = write_launch(b, stream, ev);
+  if (rc == 0) rc = (int) hipEventSynchronize(ev[3]);
+  for (int k = 0; k < 3 && rc == 0; k++) {
+    float ms = 0;
+    rc = (int) hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+    us[k] = ms * 1e3f;
+  }
+  for (int k = 0; k < 4; k++)
+    if (ev[k]) (void) hipEventDestroy(ev[k]);
+  return rc;
 }
