@@ -1426,6 +1426,145 @@ int rhp_relay_walked(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r, void 
 int rhp_relay_walked_steps(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r, void *stream, float us[3]);
 int rhp_write_responses_steps(const rhp_resp_batch_t *batch, void *stream, float us[3]);
 
+/*
+ * The requests of a proxied route re-written for the upstream: the request
+ * side's rhp_relay_walked.  batch, sessions, results and req_start are
+ * rhp_classify_sessions' arguments as the parse and the fix-up left them on
+ * `stream` (an RHP_MODE_HTTP batch whose flags are exactly
+ * RHP_BATCH_SPECULATIVE, request-major or header-major), route is its output.
+ * For every slot i < batch->n, why[i] and out_off[i + 1] - out_off[i] are
+ * written; out_off is the exclusive prefix sum of the sizes.
+ *   Forwarded.  Slot i is forwarded -- why[i] == RHP_FORWARD_OK -- when every
+ *   test below holds; otherwise its size is 0 and why[i] names the first that
+ *   failed (enum rhp_forward_why, in this order):
+ *     UNUSED    some session owns it: s is the last session with piece_lo <= i
+ *               (a bisection per slot) and piece_lo <= i < piece_lo + n_slots,
+ *               piece_lo <= piece_hi <= n, the test of rhp_classify_sessions.
+ *               Nothing of a slot that is not in use is read;
+ *     NOT_READY http[i].result == 1 and reqs[i].ret > 0;
+ *     OUTSIDE   [req_start[i], req_start[i] + ret) lies inside the session's
+ *               input [offsets[piece_lo], offsets[piece_hi]) and below
+ *               bytes_size rounded down to a multiple of 4;
+ *     CLOSED    the session's walk did not stop on -1: with last = piece_lo +
+ *               n_slots - 1, http[last].result != -1 (last < n is a slot of the
+ *               batch; a session whose n_slots runs past n is not closed and its
+ *               record is not read);
+ *     ROUTE     route[i] < n_routes and bit route[i] of forward_mask is set;
+ *     FOLD      no header record k < min(num_headers, max_headers) has name_off
+ *               == RHP_NAME_NULL (an obs-fold line has no name to write);
+ *     SPAN      method, path and every such record's name and value lie inside
+ *               [0, ret) (every parsed record does; a crafted one that does not
+ *               is never read through);
+ *     BODY      body_kind is 0 or 1 (RHP_BODY_CHUNKED_PENDING cannot remain
+ *               after the fix-up; a crafted one goes to the host);
+ *     LONG      body_len < 2^32 when body_kind == 1;
+ *     BODY_OUTSIDE  when body_kind == 1, [req_start + ret, req_start + ret +
+ *               body_len) lies inside the session's input and below bytes_size
+ *               rounded down to a multiple of 4 (Memory, below).
+ *   There is no leading-run rule: a forwarded request may stand behind one the
+ *   host answers.
+ *   THE REFERENCE HAS NO RULE HERE.  The reference writes responses
+ *   (http_write_response) and never a request, so the whole serialization is
+ *   this call's invention: the fixed text "HTTP/1.1" (the client's minor
+ *   version is not carried), which names are dropped, where Content-Length and
+ *   `extra` stand, and the CLOSED rule (the reference closes such a session,
+ *   server.c:47-51; rhp_reply_sessions answers none of it).  What ties it to the
+ *   reference is the round trip: http_read_request over a forwarded slot's
+ *   bytes gives result 1, consumed == the size, the same method, target and
+ *   body, and as fields the kept records, then Content-Length when written,
+ *   then the lines of `extra` (tests/golden/make_golden_forward.py).
+ *   Bytes.  A forwarded slot's bytes are, in order: the method bytes; one SP;
+ *   the path bytes; the 11 bytes " HTTP/1.1\r\n"; every kept header record in
+ *   order as name ": " value CRLF, name and value bytes as they lie
+ *   (http_push_field's form, http.c:63-71) -- every record is kept but for
+ *   every one, not only the first, whose name equals Content-Length,
+ *   Transfer-Encoding or one of the caller's n_names names under the classify
+ *   fold (equal lengths, a..z mapped to A..Z on both sides, no other byte);
+ *   when body_kind == 1, "Content-Length: ", body_len in decimal and CRLF (also
+ *   for length 0, and also for a chunked body the fix-up de-framed); the
+ *   extra_len bytes of `extra` as they lie; CRLF; the body_len body bytes from
+ *   req_start + ret.  body_kind == 0 writes no Content-Length line.
+ *   Order.  Slots are written in ascending index.  When out_off[n] > out_size
+ *   nothing is written to `out`; out_off, why, fwd_off and head_bits are still
+ *   complete: grow and call again.
+ *   The queue for the upstream walk.  fwd_off[s], s < n_sessions, is the number
+ *   of forwarded slots below min(piece_lo(s), n) -- with the sessions in order,
+ *   the count of forwarded slots owned by the sessions before s --
+ *   and fwd_off[n_sessions] the total.  The q-th forwarded slot in ascending
+ *   slot order sets bit q & 31 of head_bits[q >> 5] when its method is the four
+ *   bytes "HEAD" (string_equal: case matters).  Every word below (total + 31) /
+ *   32 is written whole, its bits at and above `total` clear; no word beyond
+ *   that is touched.  With one upstream connection per client session these
+ *   are rhp_walk_asked_t's req_off and head_bits as they stand.
+ * The bytes are read through bytes_rw when it is set, as rhp_classify_sessions
+ * reads them.  Contract: `sessions` ascends by piece_lo with disjoint ranges.
+ * With that order violated a slot may be reported UNUSED and fwd_off is as
+ * defined above; nothing is read outside the arguments' buffers.
+ * Memory.  Method, path, names, values and bodies are read as the aligned
+ * dwords that hold them, so OUTSIDE and BODY_OUTSIDE bound the request's and the
+ * body's end by bytes_size rounded down to 4: an end at or below a multiple of
+ * 4 stays there when it is rounded up to 4.  Nothing is written outside
+ * out_off[0, n], why[0, n), fwd_off[0, n_sessions], head_bits[0, (total + 31) /
+ * 32), work and out[0, out_off[n]).
+ * -EINVAL (rhp_forward_args.h): whatever rhp_classify_sessions refuses about the
+ * batch, sessions, results and req_start; a NULL route, f, out_off, why,
+ * fwd_off, head_bits or work; a NULL out with out_size != 0; n_routes 0 or above
+ * RHP_CLASSIFY_MAX_ROUTES; n_names above RHP_FORWARD_MAX_NAMES; a NULL text or
+ * names with n_names > 0; an empty name or one longer than
+ * RHP_CLASSIFY_NAME_MAX; extra_len above RHP_FORWARD_EXTRA_MAX; a NULL extra
+ * with extra_len > 0, or extra bytes that do not end in CRLF; out_off or work not
+ * 8-byte aligned, why, fwd_off or head_bits not 4-byte aligned (device pointers
+ * only).  n == 0 or n_sessions == 0 writes out_off[0] = 0 and fwd_off[0,
+ * n_sessions] = 0 and nothing else, by two hipMemsetAsync on `stream` and no
+ * kernel.
+ * Launch contract: seven kernels on `stream` (sizes with tile sums; two scan
+ * passes over the sizes, the same two over the forwarded counts; fwd_off and the
+ * zeroed head_bits words; copy), asynchronous, no allocation, no copy, no
+ * synchronisation; the names and `extra` travel in the kernel arguments and the
+ * caller's tables are free when the call returns; thread-safe.
+ */
+#define RHP_FORWARD_MAX_NAMES (RHP_CLASSIFY_MAX_NAMES - 2u)   /* the two built-in names take the rest */
+#define RHP_FORWARD_EXTRA_MAX 128u
+
+enum rhp_forward_why { RHP_FORWARD_OK = 0,        /* forwarded */
+                       RHP_FORWARD_UNUSED,        /* no session owns the slot */
+                       RHP_FORWARD_NOT_READY,     /* result != 1 or ret <= 0 */
+                       RHP_FORWARD_OUTSIDE,       /* the request does not lie inside its session */
+                       RHP_FORWARD_CLOSED,        /* the session's walk stopped on -1 */
+                       RHP_FORWARD_ROUTE,         /* not a forwarded route */
+                       RHP_FORWARD_FOLD,          /* an obs-fold line among the headers */
+                       RHP_FORWARD_SPAN,          /* method, path, a name or a value outside [0, ret) */
+                       RHP_FORWARD_BODY,          /* body_kind is neither 0 nor 1 */
+                       RHP_FORWARD_LONG,          /* body_len >= 2^32 */
+                       RHP_FORWARD_BODY_OUTSIDE}; /* the body does not lie inside its session */
+
+typedef struct rhp_forward {
+  uint32_t          n_routes;      /* 1..RHP_CLASSIFY_MAX_ROUTES: the classify call's n_routes */
+  uint32_t          forward_mask;  /* bit r set: route r goes upstream */
+  const uint8_t    *text;          /* host: the bytes of the caller's drop names (as rhp_walk_relay_t) */
+  const rhp_span_t *names;         /* host [n_names]: spans of `text` */
+  uint32_t          n_names;       /* 0 .. RHP_FORWARD_MAX_NAMES */
+  uint32_t          extra_len;     /* 0 .. RHP_FORWARD_EXTRA_MAX */
+  const uint8_t    *extra;         /* host, extra_len bytes: whole header lines, the last ending in CRLF */
+  uint64_t         *out_off;       /* device [n + 1]: exclusive prefix sum of the sizes, always written */
+  uint32_t         *why;           /* device [n]: enum rhp_forward_why */
+  uint8_t          *out;           /* device, out_size bytes, any alignment */
+  uint64_t          out_size;      /* out_off[n] > out_size: nothing is written to out */
+  uint32_t         *fwd_off;       /* device [n_sessions + 1] */
+  uint32_t         *head_bits;     /* device [(n + 31) / 32] at the most; (total + 31) / 32 words are written */
+  uint64_t         *work;          /* device scratch, >= RHP_FORWARD_WORK_WORDS(n, n_sessions) u64 */
+} rhp_forward_t;
+
+/* two rows of tile sums (sizes, forwarded counts), the n + 1 counts, per slot
+ * the plan the sizes step leaves the copy step (which header records are kept)
+ * and per 64 slots the HEAD flags of the forwarded ones */
+#define RHP_FORWARD_WORK_WORDS(n, n_sessions) \
+  (2u * (((uint64_t) (n) + 4095u) / 4096u + 1u) + 2u * (uint64_t) (n) + 1u + ((uint64_t) (n) + 63u) / 64u + 0u * (uint64_t) (n_sessions))
+
+int rhp_forward_sessions(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
+                         const rhp_session_result_t *results, const uint64_t *req_start,
+                         const uint16_t *route, const rhp_forward_t *f, void *stream);
+
 
 #ifdef __cplusplus
 }

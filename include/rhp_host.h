@@ -187,6 +187,18 @@ int rhp_cpu_lookup_walked(const rhp_walk_batch_t *w, const rhp_walk_lookup_t *l)
  * Sequential. */
 int rhp_cpu_relay_walked(const rhp_walk_batch_t *w, const rhp_walk_relay_t *r);
 
+/* rhp_forward_sessions (rhp.h) over a speculative batch in host memory after a
+ * host fix-up and classify: every pointer of the arguments is host memory, of
+ * any alignment for the outputs, and there is no stream.  The same out_off,
+ * why, out, fwd_off and head_bits and the same -22 (rhp_forward_args.h; the
+ * alignment rules are the device's alone).  work has to be there and is not
+ * touched.  Bytes are read one at a time: of the batch's bytes only the
+ * requests and bodies of forwarded slots, and no record of a slot that is not
+ * in use.  Sequential. */
+int rhp_cpu_forward_sessions(const rhp_batch_t *batch, const rhp_session_t *sessions, uint32_t n_sessions,
+                             const rhp_session_result_t *results, const uint64_t *req_start,
+                             const uint16_t *route, const rhp_forward_t *f);
+
 /* struct phr_header (picohttpparser.h:42-47): name == NULL for an obs-fold line */
 typedef struct rhp_phr_header {
   const char *name;

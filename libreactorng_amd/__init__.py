@@ -68,7 +68,7 @@ RHP_SYMBOLS = ("rhp_parse_batch", "rhp_set_impl", "rhp_kernel_name", "rhp_versio
                "rhp_fixup_sessions", "rhp_pack_dense", "rhp_classify_batch", "rhp_classify_sessions", "rhp_reply_sessions",
                "rhp_gather_wide", "rhp_split_sessions", "rhp_parse_messages", "rhp_decode_chunked", "rhp_frame_messages",
                "rhp_walk_responses", "rhp_walk_resume", "rhp_lookup_walked", "rhp_walk_answers", "rhp_relay_walked",
-               "rhp_relay_walked_steps", "rhp_write_responses_steps")
+               "rhp_relay_walked_steps", "rhp_write_responses_steps", "rhp_forward_sessions")
 HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_splitmix64",
                 "rhp_emu_parse_batch", "rhp_cpu_parse_batch", "rhp_phr_parse_request", "rhp_http_read_cpu",
                 "rhp_cpu_fixup_sessions", "rhp_expand_records", "rhp_expand_http", "rhp_expand_reqs", "rhp_cpu_pack_dense",
@@ -77,7 +77,8 @@ HOST_SYMBOLS = ("rhp_gen_size", "rhp_gen_fill", "rhp_gen_header_bytes", "rhp_spl
                 "rhp_cpu_split_sessions", "rhp_cpu_parse_messages", "rhp_phr_parse_response", "rhp_phr_parse_headers",
                 "rhp_cpu_decode_chunked", "rhp_phr_decode_chunked", "rhp_phr_decode_chunked_is_in_data",
                 "rhp_cpu_frame_messages", "rhp_cpu_walk_responses", "rhp_cpu_walk_resume",
-                "rhp_cpu_lookup_walked", "rhp_cpu_walk_answers", "rhp_cpu_relay_walked")
+                "rhp_cpu_lookup_walked", "rhp_cpu_walk_answers", "rhp_cpu_relay_walked",
+                "rhp_cpu_forward_sessions")
 
 _rhp = None
 _host = None
@@ -265,6 +266,28 @@ def relay_work_words(n: int) -> int:
     return (n + 4095) // 4096 + 1 + 2 * n
 
 
+class Forward(ctypes.Structure):
+    """rhp_forward_t (include/rhp.h): the forwarded routes, the drop names, the extra lines and the outputs of
+    rhp_forward_sessions"""
+    _fields_ = [("n_routes", ctypes.c_uint32), ("forward_mask", ctypes.c_uint32), ("text", ctypes.c_void_p),
+                ("names", ctypes.c_void_p), ("n_names", ctypes.c_uint32), ("extra_len", ctypes.c_uint32),
+                ("extra", ctypes.c_char_p), ("out_off", ctypes.c_void_p), ("why", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("out_size", ctypes.c_uint64), ("fwd_off", ctypes.c_void_p), ("head_bits", ctypes.c_void_p),
+                ("work", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(Forward) == 96
+FORWARD_MAX_NAMES = 14    # RHP_FORWARD_MAX_NAMES
+FORWARD_EXTRA_MAX = 128   # RHP_FORWARD_EXTRA_MAX
+(FORWARD_OK, FORWARD_UNUSED, FORWARD_NOT_READY, FORWARD_OUTSIDE, FORWARD_CLOSED, FORWARD_ROUTE, FORWARD_FOLD, FORWARD_SPAN,
+ FORWARD_BODY, FORWARD_LONG, FORWARD_BODY_OUTSIDE) = range(11)   # enum rhp_forward_why
+
+
+def forward_work_words(n: int, n_sessions: int = 0) -> int:
+    """RHP_FORWARD_WORK_WORDS (include/rhp.h)"""
+    return 2 * ((n + 4095) // 4096 + 1) + 2 * n + 1 + (n + 63) // 64
+
+
 def _torch_hip_runtime() -> str | None:
     """Path of the HIP runtime torch ships (torch/lib/libamdhip64.so), found
     without importing torch."""
@@ -359,6 +382,8 @@ def lib() -> ctypes.CDLL:
         _rhp.rhp_relay_walked.restype = ctypes.c_int
         _rhp.rhp_relay_walked_steps.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkRelay), vp, ctypes.POINTER(ctypes.c_float * 3)]
         _rhp.rhp_relay_walked_steps.restype = ctypes.c_int
+        _rhp.rhp_forward_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(Forward), vp]
+        _rhp.rhp_forward_sessions.restype = ctypes.c_int
         _rhp.rhp_write_responses_steps.argtypes = [ctypes.POINTER(RespBatch), vp, ctypes.POINTER(ctypes.c_float * 3)]
         _rhp.rhp_write_responses_steps.restype = ctypes.c_int
         _rhp.rhp_walk_answers.argtypes = [ctypes.POINTER(WalkBatch), vp, ctypes.POINTER(WalkAsked), vp]
@@ -441,6 +466,8 @@ def host() -> ctypes.CDLL:
         _host.rhp_cpu_lookup_walked.restype = ctypes.c_int
         _host.rhp_cpu_relay_walked.argtypes = [ctypes.POINTER(WalkBatch), ctypes.POINTER(WalkRelay)]
         _host.rhp_cpu_relay_walked.restype = ctypes.c_int
+        _host.rhp_cpu_forward_sessions.argtypes = [ctypes.POINTER(Batch), vp, ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(Forward)]
+        _host.rhp_cpu_forward_sessions.restype = ctypes.c_int
         _host.rhp_cpu_walk_answers.argtypes = [ctypes.POINTER(WalkBatch), vp, ctypes.POINTER(WalkAsked)]
         _host.rhp_cpu_walk_answers.restype = ctypes.c_int
     return _host
@@ -2648,3 +2675,162 @@ def relay_walked_gpu(buf, sess_off, slot_off, names=(), max_headers: int = 16, f
     if gt is not None:
         out += (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE), gt)
     return _relay_result(go.view.cpu().numpy(), gy.view.cpu().numpy(), gout.view.cpu().numpy()[: max(out_size, 0)], nt), out
+
+
+# The requests of a proxied route re-written for the upstream (rhp.h rhp_forward_sessions): the records stay where
+# the parse and the fix-up left them; out_off, why, the requests and the queue for rhp_walk_answers come back.
+
+FORWARD_POISON = 0xC3   # what out_off, why, out, fwd_off and head_bits hold before a call (tests)
+
+
+def _forward_desc(n_routes, forward_mask, names, extra, out_off, why, out, out_size, fwd_off, head_bits, work):
+    """(text, names, Forward): rhp_forward_t over classify_tables(names), the extra bytes and the outputs'
+    addresses.  The Forward points into the two arrays: keep them alive."""
+    text, nm, _ = classify_tables(names)
+    extra = bytes(extra)
+    return text, nm, Forward(n_routes, forward_mask, _ptr(text), _ptr(nm) if len(nm) else None, len(nm), len(extra),
+                             extra if extra else None, out_off, why, out, out_size, fwd_off, head_bits, work)
+
+
+def _forward_result(out_off, why, out, fwd_off, head_bits, n, n_sessions, fill=FORWARD_POISON):
+    """(out_off u64 [n + 1], why u32 [n], the requests u8 [out_off[-1]] or None when they did not fit the `out` that
+    was passed, fwd_off u32 [n_sessions + 1], head_bits u32 [(total + 31) / 32]) from the outputs' bytes; the words
+    of head_bits beyond those must still hold `fill`"""
+    off = out_off[: 8 * (n + 1)].view(np.uint64)
+    total = int(off[-1])
+    fo = fwd_off[: 4 * (n_sessions + 1)].view(np.uint32)
+    words = (int(fo[-1]) + 31) // 32
+    assert bool((head_bits[4 * words:] == fill).all()), "a word of head_bits beyond (total + 31) / 32 was written"
+    return off, why[: 4 * n].view(np.uint32), out[:total] if total <= out.size else None, fo, head_bits[: 4 * words].view(np.uint32)
+
+
+def forward_sessions_cpu(b_or_res, sessions, results, starts, route, n_routes: int, forward_mask: int, names=(),
+                         extra: bytes = b"", out_size: int | None = None):
+    """rhp_cpu_forward_sessions (include/rhp_host.h) over a speculative batch in host memory after a fix-up and a
+    classify (the Batch of speculative_cpu or a Result that describes its batch; route u16 [n] by record slot).
+    out_size None: the call runs twice, for the sizes and then with an `out` of exactly their sum.  Returns
+    (out_off, why, out, fwd_off, head_bits) as _forward_result; all five held FORWARD_POISON before the call,
+    head_bits at (n + 31) / 32 words."""
+    b = b_or_res.batch if isinstance(b_or_res, Result) else b_or_res
+    if b is None:
+        raise ValueError("this Result does not describe its batch")
+    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
+    results = np.ascontiguousarray(results, dtype=SESSION_RESULT_DTYPE)
+    starts = np.ascontiguousarray(starts, dtype=np.uint64)
+    route = np.ascontiguousarray(route, dtype=np.uint16)
+    n, ns = b.n, len(sessions)
+    work = np.zeros(forward_work_words(n, ns), dtype=np.uint64)
+
+    def run(size):
+        off = np.full(8 * (n + 1), FORWARD_POISON, dtype=np.uint8)
+        why = np.full(max(4 * n, 4), FORWARD_POISON, dtype=np.uint8)
+        out = np.full(size, FORWARD_POISON, dtype=np.uint8)
+        fo = np.full(4 * (ns + 1), FORWARD_POISON, dtype=np.uint8)
+        hb = np.full(max(4 * ((n + 31) // 32), 4), FORWARD_POISON, dtype=np.uint8)
+        *_keep, f = _forward_desc(n_routes, forward_mask, names, extra, _ptr(off), _ptr(why), _ptr(out) if size else None, size,
+                                  _ptr(fo), _ptr(hb), _ptr(work))
+        rc = host().rhp_cpu_forward_sessions(ctypes.byref(b), _ptr(sessions) if ns else None, ns, _ptr(results) if ns else None,
+                                             _ptr(starts) if ns else None, _ptr(route), ctypes.byref(f))
+        if rc != 0:
+            raise RuntimeError(f"rhp_cpu_forward_sessions failed: {rc}")
+        if n == 0 or ns == 0:   # the empty call: out_off[0] and fwd_off only
+            return np.zeros(8, dtype=np.uint8), why[:0], out, fo, hb
+        return off, why, out, fo, hb
+
+    if out_size is None:
+        out_size = int(run(0)[0].view(np.uint64)[-1])
+    return _forward_result(*run(out_size), n if ns else 0, ns)
+
+
+def forward_sessions_device(d: Batch, sessions_t, n_sessions: int, results_t, starts_t, route_t, n_routes: int,
+                            forward_mask: int, names, extra: bytes, out_off_t, why_t, out_t, out_size: int, fwd_off_t,
+                            head_bits_t, work_t, stream=None):
+    """One rhp_forward_sessions call over device tensors on the stream (default: the current one): `d` the parsed,
+    fixed-up batch's descriptor, route_t rhp_classify_sessions' output; out_off_t (8 * (n + 1) bytes, 8-byte aligned),
+    why_t (4 * n bytes), out_t (out_size bytes, any alignment; None with out_size 0), fwd_off_t (4 * (n_sessions + 1)
+    bytes), head_bits_t (4 * ((n + 31) / 32) bytes) and work_t (8 * forward_work_words(n, n_sessions) bytes).
+    Nothing is synchronised or copied (the names and the extra lines travel in the launches)."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    *_keep, f = _forward_desc(n_routes, forward_mask, names, extra, _addr(out_off_t), _addr(why_t), _addr(out_t), out_size,
+                              _addr(fwd_off_t), _addr(head_bits_t), _addr(work_t))
+    vp = ctypes.c_void_p
+    rc = lib().rhp_forward_sessions(ctypes.byref(d), vp(_addr(sessions_t)), n_sessions, vp(_addr(results_t)),
+                                    vp(_addr(starts_t)), vp(_addr(route_t)), ctypes.byref(f), vp(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_forward_sessions failed: {rc}")
+
+
+def forward_sessions_gpu(buf, off, sessions, routes, forward_mask: int, names=(), extra: bytes = b"", max_headers: int = 16,
+                         impl: int = IMPL_DFA, layout: int = LAYOUT_REQUEST_MAJOR, guard: int = 0, fill: int = FORWARD_POISON,
+                         records=None, out_size: int | None = None, out_shift: int = 0, details: bool = False):
+    """A round of split-free pipelined input forwarded on the GPU: speculative parse -> rhp_fixup_sessions ->
+    rhp_classify_sessions over `routes` -> rhp_forward_sessions, on one stream with no synchronisation in between.
+    records: (raw reqs, raw hdrs, raw http, session results, req_start, route) copied in instead of the first three
+    calls (tests: crafted records).  out_size None: the forward runs twice, for the sizes and then with an `out` of
+    exactly their sum, `out_shift` bytes off a 512-byte boundary.  Every buffer is a Guarded device buffer (guard
+    bytes on both sides, checked after the calls); the outputs hold `fill` first; requests that do not fit must leave
+    out as it was.  Returns (out_off, why, out, fwd_off, head_bits) as forward_sessions_cpu; details: also (Result,
+    session results, req_start, route u16 [n]) as the GPU left them."""
+    import torch
+    lib().rhp_set_impl(impl)
+    try:
+        db = DeviceBatch(buf, off, max_headers, MODE_HTTP, layout=layout, flags=BATCH_SPECULATIVE, guard=guard, fill=fill)
+        n, ns = db.n, len(sessions)
+        ds = torch.from_numpy(np.ascontiguousarray(sessions, dtype=SESSION_DTYPE).view(np.uint8).copy()).to("cuda") if ns else None
+        dres = Guarded("results", max(ns, 1) * SESSION_RESULT_DTYPE.itemsize, guard, fill=fill)
+        dst = Guarded("req_start", max(n, 1) * 8, guard, fill=fill)
+        droute = Guarded("route", max(n, 1) * 2, guard, fill=GUARD_BYTE)
+        go = Guarded("out_off", 8 * (n + 1), guard, fill=fill)
+        gy = Guarded("why", max(4 * n, 4), guard, fill=fill)
+        gf = Guarded("fwd_off", 4 * (ns + 1), guard, fill=fill)
+        gb = Guarded("head_bits", max(4 * ((n + 31) // 32), 4), guard, fill=fill)
+        gw = Guarded("work", 8 * forward_work_words(n, ns), guard, fill=fill)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        vp = ctypes.c_void_p
+        d = db.desc()
+        if records is not None:
+            for t, a in zip((db.reqs, db.hdrs, db.http, dres.view, dst.view, droute.view), records):
+                a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+                if a.size:
+                    t[: a.size].copy_(torch.from_numpy(a.copy()))
+        else:
+            *_keep, c = _classify_desc((), routes, None, droute.view.data_ptr())
+            db.launch()
+            rc = lib().rhp_fixup_sessions(ctypes.byref(d), vp(_addr(ds)), ns, vp(dres.view.data_ptr()), vp(dst.view.data_ptr()), stream)
+            if rc != 0:
+                raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
+            rc = lib().rhp_classify_sessions(ctypes.byref(d), vp(_addr(ds)), ns, vp(dres.view.data_ptr()), vp(dst.view.data_ptr()),
+                                             ctypes.byref(c), stream)
+            if rc != 0:
+                raise RuntimeError(f"rhp_classify_sessions failed: {rc}")
+
+        def run(n_out):
+            g = Guarded("out", max(n_out, 1), max(guard, 16) if out_shift else guard, fill=fill, shift=out_shift)
+            forward_sessions_device(d, ds, ns, dres.view, dst.view, droute.view, len(routes), forward_mask, names, extra, go.view,
+                                    gy.view, g.view if n_out else None, n_out, gf.view, gb.view, gw.view)
+            torch.cuda.synchronize()
+            return g
+
+        empty = n == 0 or ns == 0
+        if out_size is None:
+            run(0)
+            out_size = 0 if empty else int(go.view.cpu().numpy().view(np.uint64)[n])
+            for g in (go, gy, gf, gb):
+                g.view.fill_(fill)
+        gout = run(out_size)
+        if not empty and int(go.view.cpu().numpy().view(np.uint64)[n]) > out_size:
+            assert bool((gout.view == (fill or 0)).all()), "the requests do not fit, and out was written"
+        if guard:
+            db.check_guards()
+            for g in (dres, dst, droute, go, gy, gf, gb, gw, gout):
+                g.check()
+        off_b = go.view.cpu().numpy()
+        out = _forward_result(off_b[:8] if empty else off_b, gy.view.cpu().numpy(), gout.view.cpu().numpy()[: max(out_size, 0)],
+                              gf.view.cpu().numpy(), gb.view.cpu().numpy(), 0 if empty else n, ns, fill)
+        if not details:
+            return out
+        return out + (db.result(), dres.view.cpu().numpy().view(SESSION_RESULT_DTYPE)[:ns],
+                      dst.view.cpu().numpy().view(np.uint64)[:n], droute.view.cpu().numpy().view(np.uint16)[:n])
+    finally:
+        lib().rhp_set_impl(IMPL_DFA)

@@ -12,7 +12,8 @@
  * names still looked for (records only, a 65-entry mask table in LDS), and only
  * for a length match the name's bytes, read as the aligned dwords that hold
  * them, funnel-shifted, folded four at a time (SWAR a..z -> A..Z) and compared
- * with the names the host folded once.  The lookup tables travel by value in
+ * with the names the host folded once.  The lookup tables (rhp_tables.h, shared
+ * with rhp_forward.hip) travel by value in
  * the kernel argument (3.5 KiB) and the block copies them to LDS at its start:
  * no allocation, no copy, the caller's tables are free when the call returns.
  *
@@ -59,22 +60,9 @@
 #include "rhp_lookup_args.h"
 #include "rhp_relay_args.h"
 #include "rhp_scalar.h"
+#include "rhp_tables.h"
 
 namespace {
-
-constexpr uint32_t kNameDwords = RHP_CLASSIFY_NAME_MAX / 4u;
-/* route methods and targets, each starting at a dword and zero-padded to one */
-constexpr uint32_t kTextDwords = (RHP_CLASSIFY_TEXT_MAX + 2u * RHP_CLASSIFY_MAX_ROUTES * 3u) / 4u;
-
-struct CTables {
-  uint32_t name[RHP_CLASSIFY_MAX_NAMES][kNameDwords];   /* folded to upper case, zero-padded */
-  uint32_t text[kTextDwords];
-  uint16_t r_moff[RHP_CLASSIFY_MAX_ROUTES], r_mlen[RHP_CLASSIFY_MAX_ROUTES];   /* dword index into text, bytes */
-  uint16_t r_toff[RHP_CLASSIFY_MAX_ROUTES], r_tlen[RHP_CLASSIFY_MAX_ROUTES];
-  uint8_t  name_len[RHP_CLASSIFY_MAX_NAMES];
-};
-constexpr uint32_t kTabDwords = sizeof(CTables) / 4u;
-static_assert(sizeof(CTables) % 4u == 0 && offsetof(CTables, name_len) % 4u == 0, "copied to LDS as dwords");
 
 struct CParams {
   CTables         t;          /* first: the kernels read it from the start of their argument segment */
@@ -87,45 +75,6 @@ struct CParams {
 };
 static_assert(offsetof(CParams, t) == 0, "the tables lead the argument");
 static_assert(sizeof(CParams) <= 4096, "a kernel argument holds 4 KiB");
-
-/* C-locale toupper of four bytes at once: a byte in 'a'..'z' (bit 7 clear,
- * low seven bits in 0x61..0x7a) loses bit 5, every other byte stays */
-__host__ __device__ inline uint32_t fold4(uint32_t x)
-{
-  const uint32_t x7 = x & 0x7f7f7f7fu;
-  const uint32_t ge_a = x7 + 0x1f1f1f1fu, gt_z = x7 + 0x05050505u;   /* bit 7: >= 0x61, >= 0x7b (no carry out of a byte) */
-  const uint32_t is = ge_a & ~gt_z & ~x & 0x80808080u;
-  return x ^ (is >> 2);
-}
-
-/* The candidates of `cand` whose table text equals the len bytes at src:
- * candidate j's text is tab[off(j) ...], zero-padded to a dword.  Reads the
- * aligned dwords that hold the bytes, none past the one with the last byte,
- * and stops at the dword that rejects the last candidate. */
-template <bool FOLD, class Off>
-__device__ __forceinline__ uint32_t same_text(const uint8_t *src, uint32_t len, uint32_t cand, const uint32_t *tab, Off off)
-{
-  if (len == 0) return cand;
-  const uintptr_t a = (uintptr_t) src;
-  const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t) 3);
-  const uint32_t sh = (uint32_t) a & 3u, nd = (sh + len + 3u) >> 2;
-  uint32_t lo = w[0];
-  for (uint32_t j = 0; j < len && cand; j += 4) {
-    const uint32_t k = (j >> 2) + 1u;
-    const uint32_t hi = k < nd ? w[k] : 0u;
-    uint32_t x = __builtin_amdgcn_alignbyte(hi, lo, sh);
-    if (len - j < 4u) x &= (1u << (8u * (len - j))) - 1u;
-    if (FOLD) x = fold4(x);
-    for (uint32_t c = cand; c; c &= c - 1u) {
-      const uint32_t q = (uint32_t) __builtin_ctz(c);
-      if (tab[off(q) + (j >> 2)] != x) cand &= ~(1u << q);
-    }
-    lo = hi;
-  }
-  return cand;
-}
-
-typedef __attribute__((address_space(4))) uint32_t ka32;   /* a dword of the kernel argument segment */
 
 __global__ __launch_bounds__(256) void rhp_classify_kernel(CParams p)
 {
@@ -417,36 +366,6 @@ __global__ __launch_bounds__(256) void rhp_classify_sessions_kernel(SParams p)
       if (cand) rt = (uint32_t) __builtin_ctz(cand);
     }
     p.route[i] = (uint16_t) rt;
-  }
-}
-
-/* row j of the tables' names: the len bytes at s, folded to upper case */
-void pack_name(CTables &t, uint32_t j, const uint8_t *s, uint32_t len)
-{
-  uint8_t *d = reinterpret_cast<uint8_t *>(t.name[j]);
-  for (uint32_t q = 0; q < len; q++) d[q] = s[q] >= 'a' && s[q] <= 'z' ? (uint8_t) (s[q] - 0x20) : s[q];
-  t.name_len[j] = (uint8_t) len;
-}
-
-/* the caller's tables as the kernel's: names folded, route text packed */
-void pack_tables(const rhp_classify_t *c, CTables &t)
-{
-  memset(&t, 0, sizeof t);
-  for (uint32_t j = 0; j < c->n_names; j++) pack_name(t, j, c->text + c->names[j].off, c->names[j].len);
-  uint32_t at = 0;   /* dwords of t.text in use */
-  uint8_t *d = reinterpret_cast<uint8_t *>(t.text);
-  for (uint32_t r = 0; r < c->n_routes; r++) {
-    const rhp_span_t sp[2] = {c->routes[r].method, c->routes[r].target};
-    uint16_t off[2];
-    for (int q = 0; q < 2; q++) {
-      off[q] = (uint16_t) at;
-      memcpy(d + 4u * at, c->text + sp[q].off, sp[q].len);
-      at += (sp[q].len + 3u) >> 2;
-    }
-    t.r_moff[r] = off[0];
-    t.r_mlen[r] = (uint16_t) sp[0].len;
-    t.r_toff[r] = off[1];
-    t.r_tlen[r] = (uint16_t) sp[1].len;
   }
 }
 

@@ -73,7 +73,7 @@ __device__ __forceinline__ void block_sum_to(unsigned long long s, unsigned long
 }
 
 /* The two scan kernels, only in a file that defines RHP_DEVICE_SCAN_KERNELS before
- * it includes this header (rhp_writer.hip, rhp_classify.hip): every other file
+ * it includes this header (rhp_writer.hip, rhp_classify.hip, rhp_forward.hip): every other file
  * would emit and register kernels it never launches. */
 #if defined(RHP_DEVICE_SCAN_KERNELS)
 /* work[0..tiles) -> exclusive offsets (one workgroup, 1024 per round) */

@@ -2,7 +2,7 @@
  * rhp_host.cpp -- the product's host entry points (rhp_host.h): the exact
  * scalar parser over a batch in host memory, the session fix-up, the dense
  * pack and the three expansions, the host classify, reply, gather and split, the
- * message parse (responses, header blocks), their framing, the chunked decoder, the response walk, its lookup and its relay, and the pointer-based
+ * message parse (responses, header blocks), their framing, the chunked decoder, the response walk, its lookup and its relay, the forward, and the pointer-based
  * rhp_phr_parse_request / _response / _headers, rhp_phr_decode_chunked and rhp_http_read_cpu.  libreactor.so links them.  The
  * parser is rhp_scalar.h's (the code the kernel's rare paths run); where the
  * records sit and how they are encoded is rhp_records.h's.
@@ -25,6 +25,7 @@
 #include "rhp_walk_args.h"
 #include "rhp_lookup_args.h"
 #include "rhp_relay_args.h"
+#include "rhp_forward_args.h"
 #include "rhp_host_exact.h"
 
 using namespace rhp;
@@ -791,6 +792,159 @@ extern "C" int rhp_cpu_relay_walked(const rhp_walk_batch_t *w, const rhp_walk_re
   for (uint32_t i = 0; i < n; i++) {
     const RelayPlan p = relay_plan(w, r, i, head_readable, readable);
     if (p.why == RHP_RELAY_OK) d = relay_write(w, r, i, p, d);
+  }
+  return 0;
+}
+
+/* rhp_forward_sessions (rhp.h) on the host, every pointer in host memory: slot
+ * by slot the rule of rhp_forward_args.h (the kernels' own: the owner by
+ * bisection over piece_lo, the tests in rhp.h's order, the sizes), then, when
+ * everything fits, every forwarded slot's request in rhp.h's order, a byte at a
+ * time.  It shares the argument check with the launcher. */
+namespace {
+
+struct ForwardPlan {
+  uint32_t why;
+  uint64_t size, keep;   /* keep: bit k set: header record k is written */
+  bool     head;         /* the method is "HEAD" */
+};
+
+struct ForwardHost {
+  const rhp_batch_t *b;
+  const rhp_session_t *sessions;
+  uint32_t n_sessions;
+  const rhp_session_result_t *results;
+  const uint64_t *req_start;
+  const uint16_t *route;
+  const rhp_forward_t *f;
+  const uint8_t *bytes;
+  uint64_t readable;
+};
+
+ForwardPlan forward_plan(const ForwardHost &a, uint32_t i)
+{
+  ForwardPlan p = {RHP_FORWARD_UNUSED, 0, 0, false};
+  const rhp_batch_t *b = a.b;
+  const uint32_t n = b->n, m = b->max_headers;
+  uint32_t above = 0;   /* the sessions before it have piece_lo <= i */
+  for (uint32_t hi = a.n_sessions; above < hi;) {
+    const uint32_t mid = above + ((hi - above) >> 1);
+    if (a.sessions[mid].piece_lo <= i) above = mid + 1u; else hi = mid;
+  }
+  if (!above) return p;
+  const uint32_t lo = a.sessions[above - 1u].piece_lo, hi = a.sessions[above - 1u].piece_hi, ns = a.results[above - 1u].n_slots;
+  if (!rhp_forward_in_use(i, lo, hi, ns, n)) return p;
+  const rhp_req_t &r = b->reqs[i];
+  const rhp_http_t &x = b->http[i];
+  p.why = RHP_FORWARD_NOT_READY;
+  if (x.result != 1 || r.ret <= 0) return p;
+  const uint64_t rs = a.req_start[i], e = b->offsets[hi];
+  p.why = RHP_FORWARD_OUTSIDE;
+  if (!rhp_forward_inside(rs, r.ret, b->offsets[lo], e, a.readable)) return p;
+  const uint32_t last = rhp_forward_last_slot(lo, ns, n);
+  p.why = RHP_FORWARD_CLOSED;
+  if (last < n && b->http[last].result == -1) return p;
+  p.why = RHP_FORWARD_ROUTE;
+  if (!rhp_forward_route(a.route[i], a.f->n_routes, a.f->forward_mask)) return p;
+  const uint8_t *req = a.bytes + rs;
+  const uint32_t nh = r.num_headers < m ? r.num_headers : m;
+  bool fold = false, span_bad = !rhp_forward_span_inside(r.method_off, r.method_len, r.ret) || !rhp_forward_span_inside(r.path_off, r.path_len, r.ret);
+  uint64_t fields = 0;
+  for (uint32_t k = 0; k < nh; k++) {
+    const rhp_hdr_t &h = RHP_HDR(b->hdrs, b->layout, n, m, i, k);
+    if (h.name_off == RHP_NAME_NULL) { fold = true; continue; }
+    if (!rhp_forward_span_inside(h.name_off, h.name_len, r.ret) || !rhp_forward_span_inside(h.value_off, h.value_len, r.ret)) { span_bad = true; continue; }
+    if (fold || span_bad) continue;
+    const uint8_t *name = req + h.name_off;
+    bool drop = relay_same_name(name, h.name_len, (const uint8_t *) RHP_FORWARD_LENGTH_NAME, sizeof RHP_FORWARD_LENGTH_NAME - 1) ||
+                relay_same_name(name, h.name_len, (const uint8_t *) RHP_FORWARD_TE_NAME, sizeof RHP_FORWARD_TE_NAME - 1);
+    for (uint32_t j = 0; j < a.f->n_names && !drop; j++) drop = relay_same_name(name, h.name_len, a.f->text + a.f->names[j].off, a.f->names[j].len);
+    if (drop) continue;
+    p.keep |= 1ull << k;
+    fields += rhp_forward_size_field(h.name_len, h.value_len);
+  }
+  p.why = rhp_forward_why_body(fold, span_bad, x.body_kind, x.body_len, rs, r.ret, e, a.readable);
+  if (p.why != RHP_FORWARD_OK) return p;
+  p.size = rhp_forward_size_head(r.method_len, r.path_len, x.body_kind, (uint32_t) x.body_len, a.f->extra_len) + fields;
+  p.head = r.method_len == 4u && memcmp(req + r.method_off, "HEAD", 4) == 0;
+  return p;
+}
+
+/* slot i's request at d; returns the end */
+uint8_t *forward_write(const ForwardHost &a, uint32_t i, const ForwardPlan &p, uint8_t *d)
+{
+  const rhp_batch_t *b = a.b;
+  const rhp_req_t &r = b->reqs[i];
+  const rhp_http_t &x = b->http[i];
+  const uint8_t *req = a.bytes + a.req_start[i];
+  const auto text = [&](const char *s) { const size_t l = strlen(s); memcpy(d, s, l); d += l; };
+  const auto span = [&](const uint8_t *s, size_t l) { if (l) memcpy(d, s, l); d += l; };
+  span(req + r.method_off, r.method_len);
+  text(" ");
+  span(req + r.path_off, r.path_len);
+  text(" HTTP/1.1\r\n");
+  const uint32_t n = b->n, m = b->max_headers, nh = r.num_headers < m ? r.num_headers : m;
+  for (uint32_t k = 0; k < nh; k++) {
+    if (!(p.keep >> k & 1u)) continue;
+    const rhp_hdr_t &h = RHP_HDR(b->hdrs, b->layout, n, m, i, k);
+    span(req + h.name_off, h.name_len); text(": "); span(req + h.value_off, h.value_len); text("\r\n");
+  }
+  if (x.body_kind == 1u) {
+    text("Content-Length: ");
+    const uint32_t v = (uint32_t) x.body_len, L = rhp_u32_len(v);
+    for (uint32_t q = 0, y = v; q < L; q++, y /= 10u) d[L - 1u - q] = (uint8_t) ('0' + y % 10u);
+    d += L;
+    text("\r\n");
+  }
+  span(a.f->extra, a.f->extra_len);
+  text("\r\n");
+  if (x.body_kind == 1u) span(req + (uint32_t) r.ret, (size_t) x.body_len);
+  return d;
+}
+
+}  // namespace
+
+extern "C" int rhp_cpu_forward_sessions(const rhp_batch_t *b, const rhp_session_t *sessions, uint32_t n_sessions,
+                                        const rhp_session_result_t *results, const uint64_t *req_start,
+                                        const uint16_t *route, const rhp_forward_t *f)
+{
+  const int rc = rhp_forward_check(b, sessions, n_sessions, results, req_start, route, f, 0);
+  if (rc < 0) return rc;
+  const auto put32 = [](uint32_t *at, size_t k, uint32_t v) { memcpy((uint8_t *) at + 4u * k, &v, 4); };   /* (any alignment) */
+  const auto put64 = [](uint64_t *at, size_t k, uint64_t v) { memcpy((uint8_t *) at + 8u * k, &v, 8); };
+  put64(f->out_off, 0, 0);
+  if (rc != 0) {
+    for (uint32_t s = 0; s <= n_sessions; s++) put32(f->fwd_off, s, 0);
+    return 0;
+  }
+  const uint32_t n = b->n;
+  const ForwardHost a = {b, sessions, n_sessions, results, req_start, route, f, b->bytes_rw ? b->bytes_rw : b->bytes,
+                         rhp_forward_readable(b->bytes_size)};
+  std::vector<uint32_t> count((size_t) n + 1u);   /* the forwarded slots below i */
+  uint64_t total = 0;
+  uint32_t q = 0, word = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const ForwardPlan p = forward_plan(a, i);
+    count[i] = q;
+    total += p.size;
+    put32(f->why, i, p.why);
+    put64(f->out_off, (size_t) i + 1u, total);
+    if (p.why != RHP_FORWARD_OK) continue;
+    if (p.head) word |= 1u << (q & 31u);
+    if ((++q & 31u) == 0) {
+      put32(f->head_bits, (q >> 5) - 1u, word);
+      word = 0;
+    }
+  }
+  count[n] = q;
+  if (q & 31u) put32(f->head_bits, q >> 5, word);
+  for (uint32_t s = 0; s < n_sessions; s++) put32(f->fwd_off, s, count[sessions[s].piece_lo < n ? sessions[s].piece_lo : n]);
+  put32(f->fwd_off, n_sessions, q);
+  if (total > f->out_size) return 0;
+  uint8_t *d = f->out;
+  for (uint32_t i = 0; i < n; i++) {
+    const ForwardPlan p = forward_plan(a, i);
+    if (p.why == RHP_FORWARD_OK) d = forward_write(a, i, p, d);
   }
   return 0;
 }
