@@ -2155,23 +2155,147 @@ def _walk_result(results, slots, msgs, hdrs, bytes_out, n_sessions, n_slots, max
             bytes_out)
 
 
+# What the five calls of the family share (rhp_walk_batch_t), each stated once.  The *_device functions take the
+# batch as twelve arguments in the order of _walk_batch; the *_cpu and *_gpu forms get them from these helpers.
+
+
+def _walk_inputs(buf, sess_off, slot_off, n_slots_total, bytes_size, copy: bool = True):
+    """(buf u8, sess_off u64, slot_off u64, n_sessions, n_slots_total, bytes_size) as the calls take them.
+    n_slots_total None: slot_off[-1]; bytes_size None: all of buf.  copy: buf is a private copy, for the forms
+    that walk (RHP_WALK_DEFRAME writes it) or upload; without, the caller's array where it is contiguous u8."""
+    buf = np.array(buf, dtype=np.uint8) if copy else np.ascontiguousarray(buf, dtype=np.uint8)
+    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
+    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    return (buf, sess_off, slot_off, len(sess_off) - 1, int(slot_off[-1]) if n_slots_total is None else n_slots_total,
+            buf.size if bytes_size is None else bytes_size)
+
+
+def _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
+                slots_t, results_t) -> WalkBatch:
+    """rhp_walk_batch_t over numpy arrays or device tensors (None: a NULL pointer); bytes_rw is bytes.  It holds
+    addresses only: the caller keeps the arrays alive over the call."""
+    b = _addr(bytes_t)
+    return WalkBatch(b, b, bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions, n_slots_total, max_headers, flags,
+                     _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+
+
+_WALK_RECORDS = ("results", "slots", "msgs", "hdrs")   # the order of _walk_result's arguments and of a `records` tuple
+
+
+def _walk_record_sizes(n_sessions, n_slots, max_headers):
+    """the bytes of (results, slots, msgs, hdrs) as the host and the Guarded buffers are allocated: at least 1 each"""
+    return max(16 * n_sessions, 1), max(32 * n_slots, 1), max(16 * n_slots, 1), max(8 * n_slots * max_headers, 1)
+
+
+def _walk_records_host(n_sessions, n_slots, max_headers):
+    """(results, slots, msgs, hdrs) for a host walk: u8 arrays of _walk_record_sizes that hold WALK_POISON"""
+    return tuple(np.full(n, WALK_POISON, dtype=np.uint8) for n in _walk_record_sizes(n_sessions, n_slots, max_headers))
+
+
+def _walk_records_u8(records):
+    """the (results, slots, msgs, hdrs) of a `records` tuple, as a walk returned them or crafted, as flat u8 arrays"""
+    return [np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in records[:4]]
+
+
+def _walk_states(states, n_sessions):
+    """a private, contiguous copy of the states as u8 (32 bytes each); None: all zero"""
+    if states is None:
+        return np.zeros(max(32 * n_sessions, 1), dtype=np.uint8)
+    st = np.ascontiguousarray(states).view(np.uint8).reshape(-1).copy()
+    assert st.size == 32 * n_sessions, "one rhp_walk_state_t per session"
+    return st if st.size else np.zeros(1, dtype=np.uint8)
+
+
+def _walk_asked(req_off, head_bits, n_req_total):
+    """(req_off u32, head_bits u32 with at least one word, n_req_total) as the call takes them"""
+    req_off = np.ascontiguousarray(req_off, dtype=np.uint32)
+    head_bits = np.ascontiguousarray(head_bits, dtype=np.uint32).reshape(-1)
+    if head_bits.size == 0:
+        head_bits = np.zeros(1, dtype=np.uint32)
+    return req_off, head_bits, int(req_off[-1]) if n_req_total is None else n_req_total
+
+
+class _WalkDevice:
+    """The device side of a *_gpu form: the bytes and the four records as Guarded buffers (`guard` bytes on both
+    sides; the records at _walk_record_sizes, holding `fill`), sess_off and slot_off uploaded as i64.  `batch` is
+    the twelve arguments every *_device function starts with.  A form adds the buffers of its own call (add), fills
+    the records (walk), makes its own calls, synchronises once, checks every guard (check) and copies back (result)."""
+
+    def __init__(self, buf, sess_off, slot_off, max_headers, flags, guard, fill, bytes_size, n_slots_total):
+        import torch
+        buf, sess_off, slot_off, self.ns, self.nt, size = _walk_inputs(buf, sess_off, slot_off, n_slots_total, bytes_size)
+        self.max_headers, self.guard, self.fill = max_headers, guard, fill
+        self.bytes = Guarded("bytes", buf.size, guard, data=buf)
+        self.records = [Guarded(name, n, guard, fill=fill)
+                        for name, n in zip(_WALK_RECORDS, _walk_record_sizes(self.ns, self.nt, max_headers))]
+        self.states = self.answered = self.slot_req = None
+        self.guarded = [self.bytes] + self.records
+        res, slots, msgs, hdrs = (g.view for g in self.records)
+        self.batch = (self.bytes.view, size, torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda"),
+                      torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda"), self.ns, self.nt, max_headers, flags,
+                      msgs, hdrs, slots, res)
+
+    def add(self, g: Guarded) -> Guarded:
+        """one more buffer for check()"""
+        self.guarded.append(g)
+        return g
+
+    def walk(self, states=None, resume: bool = False, asked=None, slot_req: bool = False, records=None):
+        """The records filled, nothing synchronised.  records: their bytes copied in, `fill` left behind them, and no
+        walk.  Otherwise one walk: rhp_walk_answers with asked = (req_off, head_bits, n_req_total), whose queue,
+        `answered` and (slot_req) `slot_req` become Guarded buffers, the last two at least 4 bytes; else
+        rhp_walk_resume with resume or states; else rhp_walk_responses.  The states of a resumed walk: None is all
+        zero, an array is copied (_walk_states), a Guarded buffer an earlier round returned is used as it lies."""
+        import torch
+        if records is not None:
+            for g, a in zip(self.records, _walk_records_u8(records)):
+                if a.size:
+                    g.view[: a.size].copy_(torch.from_numpy(a.copy()))
+            return
+        if resume or states is not None:
+            self.states = self.add(states if isinstance(states, Guarded) else
+                                   Guarded("states", max(32 * self.ns, 1), self.guard, data=_walk_states(states, self.ns)))
+        st = self.states.view if self.states is not None else None
+        if asked is not None:
+            req_off, head_bits, nq = _walk_asked(*asked)
+            gq = self.add(Guarded("req_off", 4 * req_off.size, self.guard, data=req_off.view(np.uint8).copy()))
+            gb = self.add(Guarded("head_bits", 4 * head_bits.size, self.guard, data=head_bits.view(np.uint8).copy()))
+            self.answered = self.add(Guarded("answered", max(4 * self.ns, 4), self.guard, fill=self.fill))
+            if slot_req:
+                self.slot_req = self.add(Guarded("slot_req", max(4 * self.nt, 4), self.guard, fill=self.fill))
+            walk_answers_device(*self.batch, st, gq.view, gb.view, nq, self.answered.view,
+                                self.slot_req.view if slot_req else None)
+        elif st is not None:
+            walk_resume_device(*self.batch, st)
+        else:
+            walk_responses_device(*self.batch)
+
+    def check(self) -> None:
+        """every buffer's guard bytes (after the synchronise); nothing without guard"""
+        if self.guard:
+            for g in self.guarded:
+                g.check()
+
+    def result(self, *behind):
+        """What the walk's *_gpu form returns: _walk_result's five from the device; after a resumed walk the states
+        (WALK_STATE_DTYPE [n_sessions]) behind them and their Guarded buffer, for the next round, last; `behind`
+        between the two."""
+        res, slots, msgs, hdrs = (g.view.cpu().numpy() for g in self.records)
+        out = _walk_result(res, slots, msgs, hdrs, self.bytes.view.cpu().numpy(), self.ns, self.nt, self.max_headers)
+        if self.states is None:
+            return out + behind
+        return out + (self.states.view.cpu().numpy()[: 32 * self.ns].view(WALK_STATE_DTYPE),) + behind + (self.states,)
+
+
 def walk_responses_cpu(buf, sess_off, slot_off, max_headers: int = 16, flags: int = 0, bytes_size: int | None = None,
                        n_slots_total: int | None = None):
     """rhp_cpu_walk_responses (include/rhp_host.h): `buf` the sessions back to back with RHP_PAD zero bytes
     behind them (u8), sess_off and slot_off u64 [n_sessions + 1].  Nothing passed in is changed.  bytes_size: what
     the batch states (default: all of buf); n_slots_total: the host's copy (default: slot_off[-1]).  Returns
     (results, slots, msgs, hdrs, bytes) as _walk_result; the four records held WALK_POISON before the call."""
-    buf = np.array(buf, dtype=np.uint8)
-    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
-    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
-    ns = len(sess_off) - 1
-    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
-    res = np.full(max(16 * ns, 1), WALK_POISON, dtype=np.uint8)
-    slots = np.full(max(32 * nt, 1), WALK_POISON, dtype=np.uint8)
-    msgs = np.full(max(16 * nt, 1), WALK_POISON, dtype=np.uint8)
-    hdrs = np.full(max(8 * nt * max_headers, 1), WALK_POISON, dtype=np.uint8)
-    w = WalkBatch(_ptr(buf), _ptr(buf), buf.size if bytes_size is None else bytes_size, _ptr(sess_off), _ptr(slot_off), ns,
-                  nt, max_headers, flags, _ptr(msgs), _ptr(hdrs), _ptr(slots), _ptr(res))
+    buf, sess_off, slot_off, ns, nt, size = _walk_inputs(buf, sess_off, slot_off, n_slots_total, bytes_size)
+    res, slots, msgs, hdrs = _walk_records_host(ns, nt, max_headers)
+    w = _walk_batch(buf, size, sess_off, slot_off, ns, nt, max_headers, flags, msgs, hdrs, slots, res)
     rc = host().rhp_cpu_walk_responses(ctypes.byref(w))
     if rc != 0:
         raise RuntimeError(f"rhp_cpu_walk_responses failed: {rc}")
@@ -2187,8 +2311,8 @@ def walk_responses_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_se
     Nothing is synchronised or copied: the tensors are the call's only inputs and outputs."""
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
-    w = WalkBatch(_addr(bytes_t), _addr(bytes_t), bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions,
-                  n_slots_total, max_headers, flags, _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+    w = _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
+                    slots_t, results_t)
     rc = lib().rhp_walk_responses(ctypes.byref(w), ctypes.c_void_p(s.cuda_stream))
     if rc != 0:
         raise RuntimeError(f"rhp_walk_responses failed: {rc}")
@@ -2197,29 +2321,14 @@ def walk_responses_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_se
 def walk_responses_gpu(buf, sess_off, slot_off, max_headers: int = 16, flags: int = 0, guard: int = 0,
                        fill: int = WALK_POISON, bytes_size: int | None = None, n_slots_total: int | None = None):
     """The sessions walked on the GPU.  bytes, msgs, hdrs, slots and results are Guarded device buffers (guard
-    bytes on both sides, checked after the call); the four records hold `fill` first.  Returns what
+    bytes on both sides, checked after the call; _WalkDevice); the four records hold `fill` first.  Returns what
     walk_responses_cpu returns."""
     import torch
-    buf = np.array(buf, dtype=np.uint8)
-    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
-    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
-    ns = len(sess_off) - 1
-    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
-    db = Guarded("bytes", buf.size, guard, data=buf)
-    gm = Guarded("msgs", max(16 * nt, 1), guard, fill=fill)
-    gh = Guarded("hdrs", max(8 * nt * max_headers, 1), guard, fill=fill)
-    gs = Guarded("slots", max(32 * nt, 1), guard, fill=fill)
-    gr = Guarded("results", max(16 * ns, 1), guard, fill=fill)
-    dso = torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda")
-    dsl = torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda")
-    walk_responses_device(db.view, buf.size if bytes_size is None else bytes_size, dso, dsl, ns, nt, max_headers, flags,
-                          gm.view, gh.view, gs.view, gr.view)
+    d = _WalkDevice(buf, sess_off, slot_off, max_headers, flags, guard, fill, bytes_size, n_slots_total)
+    d.walk()
     torch.cuda.synchronize()
-    if guard:
-        for g in (db, gm, gh, gs, gr):
-            g.check()
-    return _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
-                        db.view.cpu().numpy(), ns, nt, max_headers)
+    d.check()
+    return d.result()
 
 
 # The walk carried across rounds (rhp.h rhp_walk_resume): `states` (WALK_STATE_DTYPE [n_sessions], all zero before a
@@ -2227,32 +2336,15 @@ def walk_responses_gpu(buf, sess_off, slot_off, max_headers: int = 16, flags: in
 # new bytes behind it.
 
 
-def _walk_states(states, n_sessions):
-    """a private, contiguous copy of the states as u8 (32 bytes each); None: all zero"""
-    if states is None:
-        return np.zeros(max(32 * n_sessions, 1), dtype=np.uint8)
-    st = np.ascontiguousarray(states).view(np.uint8).reshape(-1).copy()
-    assert st.size == 32 * n_sessions, "one rhp_walk_state_t per session"
-    return st if st.size else np.zeros(1, dtype=np.uint8)
-
-
 def walk_resume_cpu(buf, sess_off, slot_off, states=None, max_headers: int = 16, flags: int = 0, bytes_size: int | None = None,
                     n_slots_total: int | None = None):
     """rhp_cpu_walk_resume (include/rhp_host.h): one round.  Arguments as walk_responses_cpu, and `states`
     (WALK_STATE_DTYPE [n_sessions]; None: all zero).  Nothing passed in is changed.  Returns (results, slots, msgs,
     hdrs, bytes, states): walk_responses_cpu's five and the states the round left."""
-    buf = np.array(buf, dtype=np.uint8)
-    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
-    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
-    ns = len(sess_off) - 1
-    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
+    buf, sess_off, slot_off, ns, nt, size = _walk_inputs(buf, sess_off, slot_off, n_slots_total, bytes_size)
     st = _walk_states(states, ns)
-    res = np.full(max(16 * ns, 1), WALK_POISON, dtype=np.uint8)
-    slots = np.full(max(32 * nt, 1), WALK_POISON, dtype=np.uint8)
-    msgs = np.full(max(16 * nt, 1), WALK_POISON, dtype=np.uint8)
-    hdrs = np.full(max(8 * nt * max_headers, 1), WALK_POISON, dtype=np.uint8)
-    w = WalkBatch(_ptr(buf), _ptr(buf), buf.size if bytes_size is None else bytes_size, _ptr(sess_off), _ptr(slot_off), ns,
-                  nt, max_headers, flags, _ptr(msgs), _ptr(hdrs), _ptr(slots), _ptr(res))
+    res, slots, msgs, hdrs = _walk_records_host(ns, nt, max_headers)
+    w = _walk_batch(buf, size, sess_off, slot_off, ns, nt, max_headers, flags, msgs, hdrs, slots, res)
     rc = host().rhp_cpu_walk_resume(ctypes.byref(w), _ptr(st))
     if rc != 0:
         raise RuntimeError(f"rhp_cpu_walk_resume failed: {rc}")
@@ -2267,8 +2359,8 @@ def walk_resume_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sessi
     or copied."""
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
-    w = WalkBatch(_addr(bytes_t), _addr(bytes_t), bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions,
-                  n_slots_total, max_headers, flags, _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+    w = _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
+                    slots_t, results_t)
     rc = lib().rhp_walk_resume(ctypes.byref(w), _addr(states_t), ctypes.c_void_p(s.cuda_stream))
     if rc != 0:
         raise RuntimeError(f"rhp_walk_resume failed: {rc}")
@@ -2277,31 +2369,16 @@ def walk_resume_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sessi
 def walk_resume_gpu(buf, sess_off, slot_off, states=None, max_headers: int = 16, flags: int = 0, guard: int = 0,
                     fill: int = WALK_POISON, bytes_size: int | None = None, n_slots_total: int | None = None):
     """One round on the GPU.  bytes, msgs, hdrs, slots, results and states are Guarded device buffers (guard bytes
-    on both sides, checked after the call); the four records hold `fill` first.  `states`: WALK_STATE_DTYPE
-    [n_sessions] (None: all zero), or a Guarded buffer an earlier round returned, which is used as it lies on the
-    device.  Returns what walk_resume_cpu returns, and behind it the Guarded states buffer for the next round."""
+    on both sides, checked after the call; _WalkDevice); the four records hold `fill` first.  `states`:
+    WALK_STATE_DTYPE [n_sessions] (None: all zero), or a Guarded buffer an earlier round returned, which is used as it
+    lies on the device.  Returns what walk_resume_cpu returns, and behind it the Guarded states buffer for the next
+    round."""
     import torch
-    buf = np.array(buf, dtype=np.uint8)
-    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
-    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
-    ns = len(sess_off) - 1
-    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
-    db = Guarded("bytes", buf.size, guard, data=buf)
-    gm = Guarded("msgs", max(16 * nt, 1), guard, fill=fill)
-    gh = Guarded("hdrs", max(8 * nt * max_headers, 1), guard, fill=fill)
-    gs = Guarded("slots", max(32 * nt, 1), guard, fill=fill)
-    gr = Guarded("results", max(16 * ns, 1), guard, fill=fill)
-    gt = states if isinstance(states, Guarded) else Guarded("states", max(32 * ns, 1), guard, data=_walk_states(states, ns))
-    dso = torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda")
-    dsl = torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda")
-    walk_resume_device(db.view, buf.size if bytes_size is None else bytes_size, dso, dsl, ns, nt, max_headers, flags,
-                       gm.view, gh.view, gs.view, gr.view, gt.view)
+    d = _WalkDevice(buf, sess_off, slot_off, max_headers, flags, guard, fill, bytes_size, n_slots_total)
+    d.walk(states, resume=True)
     torch.cuda.synchronize()
-    if guard:
-        for g in (db, gm, gh, gs, gr, gt):
-            g.check()
-    return _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
-                        db.view.cpu().numpy(), ns, nt, max_headers) + (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE), gt)
+    d.check()
+    return d.result()
 
 
 # The walk told which requests were HEAD (rhp.h rhp_walk_answers): req_off (u32 [n_sessions + 1]) cuts the
@@ -2318,15 +2395,6 @@ def head_bits_of(heads) -> np.ndarray:
     return words
 
 
-def _walk_asked(req_off, head_bits, n_req_total):
-    """(req_off u32, head_bits u32 with at least one word, n_req_total) as the call takes them"""
-    req_off = np.ascontiguousarray(req_off, dtype=np.uint32)
-    head_bits = np.ascontiguousarray(head_bits, dtype=np.uint32).reshape(-1)
-    if head_bits.size == 0:
-        head_bits = np.zeros(1, dtype=np.uint32)
-    return req_off, head_bits, int(req_off[-1]) if n_req_total is None else n_req_total
-
-
 def walk_answers_cpu(buf, sess_off, slot_off, req_off, head_bits, states=None, resume: bool = False, max_headers: int = 16,
                      flags: int = 0, bytes_size: int | None = None, n_slots_total: int | None = None,
                      n_req_total: int | None = None, slot_req: bool = True):
@@ -2335,22 +2403,14 @@ def walk_answers_cpu(buf, sess_off, slot_off, req_off, head_bits, states=None, r
     (WALK_STATE_DTYPE [n_sessions]) or resume=True (all-zero states).  Nothing passed in is changed.  Returns the
     walk's tuple -- walk_responses_cpu's five, or walk_resume_cpu's six -- and behind it answered (u32 [n_sessions])
     and slot_req (u32 [n_slots_total]; None with slot_req=False); both held WALK_POISON before the call."""
-    buf = np.array(buf, dtype=np.uint8)
-    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
-    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+    buf, sess_off, slot_off, ns, nt, size = _walk_inputs(buf, sess_off, slot_off, n_slots_total, bytes_size)
     req_off, head_bits, nq = _walk_asked(req_off, head_bits, n_req_total)
-    ns = len(sess_off) - 1
-    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
     resume = resume or states is not None
     st = _walk_states(states, ns) if resume else None
-    res = np.full(max(16 * ns, 1), WALK_POISON, dtype=np.uint8)
-    slots = np.full(max(32 * nt, 1), WALK_POISON, dtype=np.uint8)
-    msgs = np.full(max(16 * nt, 1), WALK_POISON, dtype=np.uint8)
-    hdrs = np.full(max(8 * nt * max_headers, 1), WALK_POISON, dtype=np.uint8)
+    res, slots, msgs, hdrs = _walk_records_host(ns, nt, max_headers)
     ans = np.full(max(4 * ns, 1), WALK_POISON, dtype=np.uint8)
     sreq = np.full(max(4 * nt, 1), WALK_POISON, dtype=np.uint8) if slot_req else None
-    w = WalkBatch(_ptr(buf), _ptr(buf), buf.size if bytes_size is None else bytes_size, _ptr(sess_off), _ptr(slot_off), ns,
-                  nt, max_headers, flags, _ptr(msgs), _ptr(hdrs), _ptr(slots), _ptr(res))
+    w = _walk_batch(buf, size, sess_off, slot_off, ns, nt, max_headers, flags, msgs, hdrs, slots, res)
     x = WalkAsked(_ptr(req_off), _ptr(head_bits), nq, 0, _ptr(ans), _addr(sreq))
     rc = host().rhp_cpu_walk_answers(ctypes.byref(w), _addr(st), ctypes.byref(x))
     if rc != 0:
@@ -2370,8 +2430,8 @@ def walk_answers_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sess
     4-byte aligned.  Nothing is synchronised or copied."""
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
-    w = WalkBatch(_addr(bytes_t), _addr(bytes_t), bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions,
-                  n_slots_total, max_headers, flags, _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+    w = _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
+                    slots_t, results_t)
     x = WalkAsked(_addr(req_off_t), _addr(head_bits_t), n_req_total, 0, _addr(answered_t), _addr(slot_req_t))
     rc = lib().rhp_walk_answers(ctypes.byref(w), _addr(states_t), ctypes.byref(x), ctypes.c_void_p(s.cuda_stream))
     if rc != 0:
@@ -2382,45 +2442,17 @@ def walk_answers_gpu(buf, sess_off, slot_off, req_off, head_bits, states=None, r
                      flags: int = 0, guard: int = 0, fill: int = WALK_POISON, bytes_size: int | None = None,
                      n_slots_total: int | None = None, n_req_total: int | None = None, slot_req: bool = True):
     """The call on the GPU.  bytes, msgs, hdrs, slots, results, states, req_off, head_bits, answered and slot_req
-    are Guarded device buffers (guard bytes on both sides, checked after the call); the records, answered and
-    slot_req hold `fill` first.  `states`: as walk_resume_gpu takes them (a Guarded buffer an earlier round returned
+    are Guarded device buffers (guard bytes on both sides, checked after the call; _WalkDevice); the records,
+    answered and slot_req hold `fill` first.  `states`: as walk_resume_gpu takes them (a Guarded buffer an earlier round returned
     is used as it lies on the device); resume=True with states None: all-zero states.  Returns what
     walk_answers_cpu returns; with states, the Guarded states buffer for the next round comes last."""
     import torch
-    buf = np.array(buf, dtype=np.uint8)
-    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
-    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
-    req_off, head_bits, nq = _walk_asked(req_off, head_bits, n_req_total)
-    ns = len(sess_off) - 1
-    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
-    resume = resume or states is not None
-    db = Guarded("bytes", buf.size, guard, data=buf)
-    gm = Guarded("msgs", max(16 * nt, 1), guard, fill=fill)
-    gh = Guarded("hdrs", max(8 * nt * max_headers, 1), guard, fill=fill)
-    gs = Guarded("slots", max(32 * nt, 1), guard, fill=fill)
-    gr = Guarded("results", max(16 * ns, 1), guard, fill=fill)
-    gt = None
-    if resume:
-        gt = states if isinstance(states, Guarded) else Guarded("states", max(32 * ns, 1), guard, data=_walk_states(states, ns))
-    gq = Guarded("req_off", 4 * req_off.size, guard, data=req_off.view(np.uint8).copy())
-    gb = Guarded("head_bits", 4 * head_bits.size, guard, data=head_bits.view(np.uint8).copy())
-    ga = Guarded("answered", max(4 * ns, 4), guard, fill=fill)
-    gl = Guarded("slot_req", max(4 * nt, 4), guard, fill=fill) if slot_req else None
-    dso = torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda")
-    dsl = torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda")
-    walk_answers_device(db.view, buf.size if bytes_size is None else bytes_size, dso, dsl, ns, nt, max_headers, flags,
-                        gm.view, gh.view, gs.view, gr.view, gt.view if resume else None, gq.view, gb.view, nq, ga.view,
-                        gl.view if slot_req else None)
+    d = _WalkDevice(buf, sess_off, slot_off, max_headers, flags, guard, fill, bytes_size, n_slots_total)
+    d.walk(states, resume, (req_off, head_bits, n_req_total), slot_req)
     torch.cuda.synchronize()
-    if guard:
-        for g in (db, gm, gh, gs, gr, gq, gb, ga) + ((gt,) if resume else ()) + ((gl,) if slot_req else ()):
-            g.check()
-    out = _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
-                       db.view.cpu().numpy(), ns, nt, max_headers)
-    if resume:
-        out += (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE),)
-    out += (ga.view.cpu().numpy()[: 4 * ns].view(np.uint32), gl.view.cpu().numpy()[: 4 * nt].view(np.uint32) if slot_req else None)
-    return out + ((gt,) if resume else ())
+    d.check()
+    return d.result(d.answered.view.cpu().numpy()[: 4 * d.ns].view(np.uint32),
+                    d.slot_req.view.cpu().numpy()[: 4 * d.nt].view(np.uint32) if slot_req else None)
 
 
 # The header lookup over the slots of a walk (rhp.h rhp_lookup_walked): the records stay where the walk left
@@ -2440,17 +2472,11 @@ def lookup_walked_cpu(records, buf, sess_off, slot_off, names, max_headers: int 
     walk_responses_cpu or walk_resume_cpu returned them (their first four), or crafted ones; buf, sess_off and
     slot_off as that walk got them (buf may be the bytes it left).  Returns fields FIELDREF_DTYPE [n_names,
     n_slots_total]; it held LOOKUP_POISON before the call."""
-    buf = np.ascontiguousarray(buf, dtype=np.uint8)
-    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
-    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
-    ns = len(sess_off) - 1
-    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
-    res, slots, msgs, hdrs = (np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in records[:4])
+    buf, sess_off, slot_off, ns, nt, size = _walk_inputs(buf, sess_off, slot_off, n_slots_total, bytes_size, copy=False)
+    res, slots, msgs, hdrs = (a if a.size else None for a in _walk_records_u8(records))   # an empty record array: NULL
     text, nm, _ = classify_tables(names)
     fields = np.full(max(4 * len(nm) * nt, 1), LOOKUP_POISON, dtype=np.uint8)
-    w = WalkBatch(_ptr(buf), _ptr(buf), buf.size if bytes_size is None else bytes_size, _ptr(sess_off), _ptr(slot_off), ns,
-                  nt, max_headers, flags, _ptr(msgs) if msgs.size else None, _ptr(hdrs) if hdrs.size else None,
-                  _ptr(slots) if slots.size else None, _ptr(res) if res.size else None)
+    w = _walk_batch(buf, size, sess_off, slot_off, ns, nt, max_headers, flags, msgs, hdrs, slots, res)
     l = WalkLookup(_ptr(text), _ptr(nm), len(nm), 0, _ptr(fields))
     rc = host().rhp_cpu_lookup_walked(ctypes.byref(w), ctypes.byref(l))
     if rc != 0:
@@ -2467,8 +2493,8 @@ def lookup_walked_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_ses
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
     text, nm, _ = classify_tables(names)
-    w = WalkBatch(_addr(bytes_t), _addr(bytes_t), bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions,
-                  n_slots_total, max_headers, flags, _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+    w = _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
+                    slots_t, results_t)
     l = WalkLookup(_ptr(text), _ptr(nm), len(nm), 0, _addr(fields_t))
     rc = lib().rhp_lookup_walked(ctypes.byref(w), ctypes.byref(l), ctypes.c_void_p(s.cuda_stream))
     if rc != 0:
@@ -2486,43 +2512,13 @@ def lookup_walked_gpu(buf, sess_off, slot_off, names, max_headers: int = 16, fla
     in front, `fill` behind them).  Returns (fields as lookup_walked_cpu, what walk_responses_gpu or
     walk_resume_gpu returns)."""
     import torch
-    buf = np.array(buf, dtype=np.uint8)
-    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
-    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
-    ns, nn = len(sess_off) - 1, len(names)
-    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
-    resume = resume or states is not None
-    size = buf.size if bytes_size is None else bytes_size
-    db = Guarded("bytes", buf.size, guard, data=buf)
-    gm = Guarded("msgs", max(16 * nt, 1), guard, fill=fill)
-    gh = Guarded("hdrs", max(8 * nt * max_headers, 1), guard, fill=fill)
-    gs = Guarded("slots", max(32 * nt, 1), guard, fill=fill)
-    gr = Guarded("results", max(16 * ns, 1), guard, fill=fill)
-    gf = Guarded("fields", max(4 * nn * nt, 1), guard, fill=fill)
-    gt = None
-    if resume and records is None:
-        gt = states if isinstance(states, Guarded) else Guarded("states", max(32 * ns, 1), guard, data=_walk_states(states, ns))
-    dso = torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda")
-    dsl = torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda")
-    if records is not None:
-        for g, a in zip((gr, gs, gm, gh), records[:4]):
-            a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-            if a.size:
-                g.view[: a.size].copy_(torch.from_numpy(a.copy()))
-    elif resume:
-        walk_resume_device(db.view, size, dso, dsl, ns, nt, max_headers, flags, gm.view, gh.view, gs.view, gr.view, gt.view)
-    else:
-        walk_responses_device(db.view, size, dso, dsl, ns, nt, max_headers, flags, gm.view, gh.view, gs.view, gr.view)
-    lookup_walked_device(db.view, size, dso, dsl, ns, nt, max_headers, flags, gm.view, gh.view, gs.view, gr.view, names, gf.view)
+    d = _WalkDevice(buf, sess_off, slot_off, max_headers, flags, guard, fill, bytes_size, n_slots_total)
+    gf = d.add(Guarded("fields", max(4 * len(names) * d.nt, 1), guard, fill=fill))
+    d.walk(states, resume, records=records)
+    lookup_walked_device(*d.batch, names, gf.view)
     torch.cuda.synchronize()
-    if guard:
-        for g in (db, gm, gh, gs, gr, gf) + ((gt,) if gt is not None else ()):
-            g.check()
-    out = _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
-                       db.view.cpu().numpy(), ns, nt, max_headers)
-    if gt is not None:
-        out += (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE), gt)
-    return _lookup_fields(gf.view.cpu().numpy(), nn, nt), out
+    d.check()
+    return _lookup_fields(gf.view.cpu().numpy(), len(names), d.nt), d.result()
 
 
 # The walked responses re-written for the client side (rhp.h rhp_relay_walked): the records stay where the walk
@@ -2546,17 +2542,11 @@ def relay_walked_cpu(records, buf, sess_off, slot_off, names=(), max_headers: in
     returned them (its first four), or crafted ones; buf the bytes that walk left (its fifth), sess_off, slot_off
     and flags as it got them.  out_size None: the call runs twice, for the sizes and then with an `out` of exactly
     their sum.  Returns (out_off, why, out) as _relay_result; all three held RELAY_POISON before the call."""
-    buf = np.ascontiguousarray(buf, dtype=np.uint8)
-    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
-    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
-    ns = len(sess_off) - 1
-    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
-    res, slots, msgs, hdrs = (np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in records[:4])
+    buf, sess_off, slot_off, ns, nt, size = _walk_inputs(buf, sess_off, slot_off, n_slots_total, bytes_size, copy=False)
+    res, slots, msgs, hdrs = (a if a.size else None for a in _walk_records_u8(records))   # an empty record array: NULL
     text, nm, _ = classify_tables(names)
     work = np.zeros(relay_work_words(nt), dtype=np.uint64)
-    w = WalkBatch(_ptr(buf), _ptr(buf), buf.size if bytes_size is None else bytes_size, _ptr(sess_off), _ptr(slot_off), ns,
-                  nt, max_headers, flags, _ptr(msgs) if msgs.size else None, _ptr(hdrs) if hdrs.size else None,
-                  _ptr(slots) if slots.size else None, _ptr(res) if res.size else None)
+    w = _walk_batch(buf, size, sess_off, slot_off, ns, nt, max_headers, flags, msgs, hdrs, slots, res)
 
     def run(size):
         off = np.full(8 * (nt + 1), RELAY_POISON, dtype=np.uint8)
@@ -2585,8 +2575,8 @@ def relay_walked_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sess
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
     text, nm, _ = classify_tables(names)
-    w = WalkBatch(_addr(bytes_t), _addr(bytes_t), bytes_size, _addr(sess_off_t), _addr(slot_off_t), n_sessions,
-                  n_slots_total, max_headers, flags, _addr(msgs_t), _addr(hdrs_t), _addr(slots_t), _addr(results_t))
+    w = _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
+                    slots_t, results_t)
     r = WalkRelay(_ptr(text), _ptr(nm) if len(nm) else None, len(nm), len(date), date, _addr(out_off_t), _addr(why_t),
                   _addr(out_t), out_size, _addr(work_t))
     if steps:
@@ -2609,53 +2599,20 @@ def relay_walked_gpu(buf, sess_off, slot_off, names=(), max_headers: int = 16, f
     records: (results, slots, msgs, hdrs) copied in instead of walking (tests: crafted records).  out_size None:
     the relay runs twice, for the sizes and then with an `out` of exactly their sum, `out_shift` bytes off a
     512-byte boundary.  Every buffer is a Guarded device buffer (guard bytes on both sides, checked after the
-    calls); out_off, why and out hold `fill` first; steps: the call that writes the replies is rhp_relay_walked_steps;
+    calls; the walk's by _WalkDevice); out_off, why and out hold `fill` first; steps: the call that writes the replies is rhp_relay_walked_steps;
     replies that do not fit must leave out as it was.  Returns ((out_off, why, out) as relay_walked_cpu, what the
     walk's *_gpu function returns up to the states)."""
     import torch
-    buf = np.array(buf, dtype=np.uint8)
-    sess_off = np.ascontiguousarray(sess_off, dtype=np.uint64)
-    slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
-    ns = len(sess_off) - 1
-    nt = int(slot_off[-1]) if n_slots_total is None else n_slots_total
-    resume = resume or states is not None
-    size = buf.size if bytes_size is None else bytes_size
-    db = Guarded("bytes", buf.size, guard, data=buf)
-    gm = Guarded("msgs", max(16 * nt, 1), guard, fill=fill)
-    gh = Guarded("hdrs", max(8 * nt * max_headers, 1), guard, fill=fill)
-    gs = Guarded("slots", max(32 * nt, 1), guard, fill=fill)
-    gr = Guarded("results", max(16 * ns, 1), guard, fill=fill)
-    go = Guarded("out_off", 8 * (nt + 1), guard, fill=fill)
-    gy = Guarded("why", max(4 * nt, 4), guard, fill=fill)
-    gw = Guarded("work", 8 * relay_work_words(nt), guard, fill=fill)
-    extra = []
-    gt = None
-    if resume and records is None:
-        gt = states if isinstance(states, Guarded) else Guarded("states", max(32 * ns, 1), guard, data=_walk_states(states, ns))
-        extra.append(gt)
-    dso = torch.from_numpy(sess_off.view(np.int64).copy()).to("cuda")
-    dsl = torch.from_numpy(slot_off.view(np.int64).copy()).to("cuda")
-    batch = (db.view, size, dso, dsl, ns, nt, max_headers, flags, gm.view, gh.view, gs.view, gr.view)
-    if records is not None:
-        for g, a in zip((gr, gs, gm, gh), records[:4]):
-            a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-            if a.size:
-                g.view[: a.size].copy_(torch.from_numpy(a.copy()))
-    elif asked is not None:
-        req_off, head_bits, nq = _walk_asked(*asked)
-        gq = Guarded("req_off", 4 * req_off.size, guard, data=req_off.view(np.uint8).copy())
-        gb = Guarded("head_bits", 4 * head_bits.size, guard, data=head_bits.view(np.uint8).copy())
-        ga = Guarded("answered", max(4 * ns, 4), guard, fill=fill)
-        extra += [gq, gb, ga]
-        walk_answers_device(*batch, gt.view if resume else None, gq.view, gb.view, nq, ga.view, None)
-    elif resume:
-        walk_resume_device(*batch, gt.view)
-    else:
-        walk_responses_device(*batch)
+    d = _WalkDevice(buf, sess_off, slot_off, max_headers, flags, guard, fill, bytes_size, n_slots_total)
+    nt = d.nt
+    go = d.add(Guarded("out_off", 8 * (nt + 1), guard, fill=fill))
+    gy = d.add(Guarded("why", max(4 * nt, 4), guard, fill=fill))
+    gw = d.add(Guarded("work", 8 * relay_work_words(nt), guard, fill=fill))
+    d.walk(states, resume, asked, records=records)
 
     def run(n_out):
         g = Guarded("out", max(n_out, 1), max(guard, 16) if out_shift else guard, fill=fill, shift=out_shift)
-        relay_walked_device(*batch, names, go.view, gy.view, g.view if n_out else None, n_out, gw.view, date, steps=steps and n_out > 0)
+        relay_walked_device(*d.batch, names, go.view, gy.view, g.view if n_out else None, n_out, gw.view, date, steps=steps and n_out > 0)
         torch.cuda.synchronize()
         return g
 
@@ -2667,14 +2624,9 @@ def relay_walked_gpu(buf, sess_off, slot_off, names=(), max_headers: int = 16, f
     gout = run(out_size)
     if int(go.view.cpu().numpy().view(np.uint64)[nt]) > out_size:
         assert bool((gout.view == (fill or 0)).all()), "the replies do not fit, and out was written"
-    if guard:
-        for g in [db, gm, gh, gs, gr, go, gy, gw, gout] + extra:
-            g.check()
-    out = _walk_result(gr.view.cpu().numpy(), gs.view.cpu().numpy(), gm.view.cpu().numpy(), gh.view.cpu().numpy(),
-                       db.view.cpu().numpy(), ns, nt, max_headers)
-    if gt is not None:
-        out += (gt.view.cpu().numpy()[: 32 * ns].view(WALK_STATE_DTYPE), gt)
-    return _relay_result(go.view.cpu().numpy(), gy.view.cpu().numpy(), gout.view.cpu().numpy()[: max(out_size, 0)], nt), out
+    d.add(gout)
+    d.check()
+    return _relay_result(go.view.cpu().numpy(), gy.view.cpu().numpy(), gout.view.cpu().numpy()[: max(out_size, 0)], nt), d.result()
 
 
 # The requests of a proxied route re-written for the upstream (rhp.h rhp_forward_sessions): the records stay where

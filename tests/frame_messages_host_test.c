@@ -16,76 +16,10 @@
  * that point past their message and past the batch's bytes, and the refusals.
  * Exits non-zero on the first mismatch.
  */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "rhp.h"
 #include "rhp_host.h"
 
-#define FAIL(...) do { printf("frame_messages_host_test: " __VA_ARGS__); printf("\n"); return 1; } while (0)
-
-static uint8_t *g_file;
-static size_t g_size;
-
-static uint32_t rd16(const uint8_t *p) { return (uint32_t) p[0] | (uint32_t) p[1] << 8; }
-static uint32_t rd32(const uint8_t *p) { return rd16(p) | rd16(p + 2) << 16; }
-static uint64_t rd64(const uint8_t *p) { return (uint64_t) rd32(p) | (uint64_t) rd32(p + 4) << 32; }
-
-/* The data of member `name`.npy of the stored (not compressed) zip in g_file,
- * copied into an allocation of exactly its size; *count = its elements of
- * `elem` bytes, whose dtype string must be `descr`.  NULL: not found / not
- * understood. */
-static void *npz_array(const char *name, const char *descr, size_t elem, size_t *count)
-{
-  char want[64];
-  snprintf(want, sizeof want, "%s.npy", name);
-  size_t at = 0;
-  while (at + 30 <= g_size && rd32(g_file + at) == 0x04034b50u) {   /* a local file header */
-    const uint8_t *h = g_file + at;
-    const uint32_t flags = rd16(h + 6), method = rd16(h + 8), nlen = rd16(h + 26), xlen = rd16(h + 28);
-    uint64_t csize = rd32(h + 18), usize = rd32(h + 22);
-    if (at + 30 + nlen + xlen > g_size) return NULL;
-    const uint8_t *x = h + 30 + nlen;
-    for (uint32_t q = 0; q + 4 <= xlen;) {   /* zip64: the sizes are in the extra field */
-      const uint32_t id = rd16(x + q), len = rd16(x + q + 2);
-      if (q + 4 + len > xlen) return NULL;
-      if (id == 1 && len >= 16 && usize == 0xffffffffu) {
-        usize = rd64(x + q + 4);
-        csize = rd64(x + q + 12);
-      }
-      q += 4 + len;
-    }
-    const size_t data = at + 30 + nlen + xlen;
-    if ((flags & 8u) || method != 0 || csize != usize || csize > g_size - data) return NULL;
-    if (nlen == strlen(want) && memcmp(h + 30, want, nlen) == 0) {
-      const uint8_t *d = g_file + data;
-      if (usize < 12 || memcmp(d, "\x93NUMPY", 6) != 0) return NULL;
-      const size_t hl = d[6] == 1 ? 10 + rd16(d + 8) : 12 + rd32(d + 8);
-      if (hl > usize) return NULL;
-      char head[512];
-      const size_t tl = hl < sizeof head ? hl : sizeof head - 1;
-      memcpy(head, d, tl);
-      for (size_t i = 0; i < tl; i++) if (!head[i]) head[i] = ' ';
-      head[tl] = 0;
-      if (!strstr(head + 10, descr) || strstr(head + 10, "'fortran_order': True")) return NULL;
-      const size_t bytes = (size_t) usize - hl;
-      if (bytes % elem) return NULL;
-      *count = bytes / elem;
-      void *out = malloc(bytes ? bytes : 1);
-      if (out && bytes) memcpy(out, d + hl, bytes);
-      return out;
-    }
-    at = data + (size_t) csize;
-  }
-  return NULL;
-}
-
-#define LOAD(var, type, descr) \
-  size_t n_##var = 0; \
-  type *var = (type *) npz_array(#var, descr, sizeof(type), &n_##var); \
-  if (!var) FAIL("%s: array '%s' (%s) not found", path, #var, descr)
+#define HOST_TEST_NAME "frame_messages_host_test"
+#include "host_test.h"
 
 static const char kMsg[] = "HTTP/1.1 200 OK\r\nContent-Length: 25\r\nConnection: close\r\n\r\n";   /* 58 bytes */
 
@@ -209,14 +143,7 @@ static int refusals(void)
 int main(int argc, char **argv)
 {
   const char *path = argc > 1 ? argv[1] : "../../tests/golden/frame_messages.npz";
-  FILE *fp = fopen(path, "rb");
-  if (!fp) FAIL("cannot open %s", path);
-  fseek(fp, 0, SEEK_END);
-  g_size = (size_t) ftell(fp);
-  fseek(fp, 0, SEEK_SET);
-  g_file = (uint8_t *) malloc(g_size);
-  if (!g_file || fread(g_file, 1, g_size, fp) != g_size) FAIL("cannot read %s", path);
-  fclose(fp);
+  if (npz_open(path)) return 1;
 
   LOAD(set_kind, uint32_t, "'<u4'");
   LOAD(set_maxh, uint32_t, "'<u4'");

@@ -1,7 +1,7 @@
 /*
  * walk_edges_host.h -- the cases of tests/golden/walk_edges.npz for the two
  * stand-alone host programs (walk_responses_host_test.c, walk_resume_host_test.c),
- * which include it behind their own npz_array, LOAD, FAIL and all_poison.
+ * which include it behind host_test.h (npz_open, LOAD, FAIL and all_poison).
  *
  * The file (tests/golden/make_golden_walk_edges.py names its arrays) holds calls
  * whose bytes_size puts the readable end at every byte of a session's last
@@ -20,14 +20,7 @@ static int walk_edges(const char *path, int which, size_t *cases_run)   /* which
 {
   uint8_t *const old_file = g_file;
   const size_t old_size = g_size;
-  FILE *fp = fopen(path, "rb");
-  if (!fp) FAIL("cannot open %s", path);
-  fseek(fp, 0, SEEK_END);
-  g_size = (size_t) ftell(fp);
-  fseek(fp, 0, SEEK_SET);
-  g_file = (uint8_t *) malloc(g_size);
-  if (!g_file || fread(g_file, 1, g_size, fp) != g_size) FAIL("cannot read %s", path);
-  fclose(fp);
+  if (npz_open(path)) return 1;   /* a second file: the program's own is put back at the end */
   LOAD(kind_state, uint8_t, "|u1"); LOAD(max_headers, uint32_t, "<u4"); LOAD(flags, uint32_t, "<u4"); LOAD(slot_off, uint64_t, "<u8");
   LOAD(lead, uint8_t, "|u1"); LOAD(tail, uint8_t, "|u1"); LOAD(tail_sess, uint32_t, "<u4"); LOAD(buf_kind, uint8_t, "|u1");
   LOAD(buf_byte, uint32_t, "<u4"); LOAD(buf_a, uint16_t, "<u2"); LOAD(mid, uint8_t, "|u1");

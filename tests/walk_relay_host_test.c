@@ -15,24 +15,11 @@
  * hand whose spans and bodies point outside, an out one byte short, and the
  * refusals.  Exits non-zero on the first mismatch.
  */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "rhp.h"
 #include "rhp_host.h"
 
-#if defined(__SANITIZE_ADDRESS__)
-#include <sanitizer/asan_interface.h>
-#define POISON(p, n) ASAN_POISON_MEMORY_REGION(p, n)
-#define UNPOISON(p, n) ASAN_UNPOISON_MEMORY_REGION(p, n)
-#else
-#define POISON(p, n) ((void) (p), (void) (n))
-#define UNPOISON(p, n) ((void) (p), (void) (n))
-#endif
+#define HOST_TEST_NAME "walk_relay_host_test"
+#include "host_test.h"
 
-#define FAIL(...) do { printf("walk_relay_host_test: " __VA_ARGS__); printf("\n"); return 1; } while (0)
 #define DATE "Wed, 16 Aug 2023 10:29:23 GMT"
 #define HEAD(status, type, len) "HTTP/1.1 " status "\r\nServer: *\r\nDate: " DATE "\r\nContent-Type: " type "\r\nContent-Length: " len "\r\n"
 
