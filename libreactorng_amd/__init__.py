@@ -1150,6 +1150,39 @@ def fixup_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_DFA, l
         lib().rhp_set_impl(IMPL_DFA)
 
 
+def fixup_sessions_device(d: Batch, sessions_t, n_sessions: int, results_t, starts_t, stream=None):
+    """One rhp_fixup_sessions call over device tensors on the stream (default: the current one): `d` the
+    speculative batch's descriptor as rhp_parse_batch left it, sessions_t (8 * n_sessions bytes); the session
+    results are left in results_t (16 * n_sessions bytes) and req_start in starts_t (8 * n bytes).  Nothing is
+    synchronised or copied: the tensors are the call's only inputs and outputs."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    vp = ctypes.c_void_p
+    rc = lib().rhp_fixup_sessions(ctypes.byref(d), vp(_addr(sessions_t)), n_sessions, vp(_addr(results_t)),
+                                  vp(_addr(starts_t)), vp(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
+
+
+def classify_sessions_device(d: Batch, sessions_t, n_sessions: int, results_t, starts_t, fields_t, route_t, names=(), routes=(),
+                             *, tables=None, stream=None):
+    """One rhp_classify_sessions call over device tensors on the stream (default: the current one): `d` the batch's
+    descriptor after the fix-up, whose results_t and starts_t it reads; fields_t (4 * n_names * n bytes) and route_t
+    (2 * n bytes) are the outputs.  The host tables are classify_tables(names, routes), or `tables`: (text, names,
+    routes) as that function returns them, where the caller owns the arrays (they may be freed or overwritten once
+    the call has returned).  Nothing is synchronised or copied."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
+    text, nm, rt = tables if tables is not None else classify_tables(names, routes)
+    c = Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm), len(rt),
+                 _addr(fields_t) if len(nm) else None, _addr(route_t) if len(rt) else None)
+    vp = ctypes.c_void_p
+    rc = lib().rhp_classify_sessions(ctypes.byref(d), vp(_addr(sessions_t)), n_sessions, vp(_addr(results_t)),
+                                     vp(_addr(starts_t)), ctypes.byref(c), vp(s.cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"rhp_classify_sessions failed: {rc}")
+
+
 def classify_sessions_cpu(b_or_res, sessions, results, starts, names, routes=()):
     """rhp_cpu_classify_sessions (include/rhp_host.h) over a speculative batch in
     host memory after a fix-up: the Batch of speculative_cpu, or a Result that
@@ -1638,16 +1671,19 @@ def gather_wide_device(d: Batch, sessions_t, n_sessions: int, results_t, starts_
     return finish
 
 
-def pack_dense_device(db: "DeviceBatch", guard: int = 0):
-    """rhp_pack_dense over the device records of `db` as they are now, on the current stream: the three outputs
-    as Guarded device buffers (dreq 8n, hc 8n, lens16 2 * max_headers * n bytes), holding WIDE_POISON first."""
+def pack_dense_device(db: "DeviceBatch", guard: int = 0, stream=None, outs=None):
+    """rhp_pack_dense over the device records of `db` as they are now, on the stream (default: the current one): the
+    three outputs as Guarded device buffers (dreq 8n, hc 8n, lens16 2 * max_headers * n bytes), holding WIDE_POISON
+    first.  outs: (dreq, hc, lens16) device tensors of those sizes that the caller made instead; nothing is then
+    allocated or filled, and they are returned.  `db`: a DeviceBatch, or anything with its n, max_headers and desc()."""
     import torch
+    s = stream if stream is not None else torch.cuda.current_stream()
     n, m = db.n, db.max_headers
-    outs = [Guarded(name, max(size, 8), guard, fill=WIDE_POISON) for name, size in
-            (("dreq", 8 * n), ("hc", 8 * n), ("lens16", 2 * m * n))]
+    if outs is None:
+        outs = [Guarded(name, max(size, 8), guard, fill=WIDE_POISON) for name, size in
+                (("dreq", 8 * n), ("hc", 8 * n), ("lens16", 2 * m * n))]
     d = db.desc()
-    rc = lib().rhp_pack_dense(ctypes.byref(d), outs[0].view.data_ptr(), outs[1].view.data_ptr(), outs[2].view.data_ptr(),
-                              torch.cuda.current_stream().cuda_stream)
+    rc = lib().rhp_pack_dense(ctypes.byref(d), *(_addr(o.view if isinstance(o, Guarded) else o) for o in outs), s.cuda_stream)
     if rc != 0:
         raise RuntimeError(f"rhp_pack_dense failed: {rc}")
     return outs
