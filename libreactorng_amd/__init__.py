@@ -11,6 +11,7 @@ Reference interface mirrored (record fields are offsets from each request start)
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from dataclasses import dataclass
@@ -525,6 +526,29 @@ def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
 
 
+def _stream(stream=None) -> ctypes.c_void_p:
+    """the stream as the library's calls take it; None: the current one"""
+    import torch
+    return ctypes.c_void_p((stream if stream is not None else torch.cuda.current_stream()).cuda_stream)
+
+
+@contextlib.contextmanager
+def _impl(impl: int):
+    """the parse kernel's implementation set for the block, IMPL_DFA again behind it"""
+    lib().rhp_set_impl(impl)
+    try:
+        yield
+    finally:
+        lib().rhp_set_impl(IMPL_DFA)
+
+
+def _aligned(size: int, shift: int = 0, fill: int = 0) -> np.ndarray:
+    """`size` host bytes that hold `fill` and start `shift` bytes behind a 16-byte boundary"""
+    raw = np.full(size + shift + 16, fill, dtype=np.uint8)
+    at = (-raw.ctypes.data) % 16 + shift
+    return raw[at: at + size]
+
+
 def generate(config: int, n: int, seed: int, lo: int = 0):
     """Requests [lo, lo+n) of a generator config -> (bytes uint8[size+RHP_PAD], offsets uint64[n+1])."""
     h = host()
@@ -863,13 +887,11 @@ class DeviceBatch:
     _runtime_checked = False   # one /proc/self/maps scan per process (it costs ~0.2 ms: not per launch)
 
     def launch(self, stream=None) -> None:
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
         d = self.desc()
         if not DeviceBatch._runtime_checked:
             check_one_hip_runtime()   # the device buffers were allocated by torch's runtime by now
             DeviceBatch._runtime_checked = True
-        rc = lib().rhp_parse_batch(ctypes.byref(d), ctypes.c_void_p(s.cuda_stream))
+        rc = lib().rhp_parse_batch(ctypes.byref(d), _stream(stream))
         if rc != 0:
             raise RuntimeError(f"rhp_parse_batch failed: {rc}")
 
@@ -907,8 +929,7 @@ class DeviceBatch:
         d = self.desc()
 
         def launch(stream=None, _keep=keep):
-            s = stream if stream is not None else torch.cuda.current_stream()
-            rc = lib().rhp_classify_batch(ctypes.byref(d), ctypes.byref(c), ctypes.c_void_p(s.cuda_stream))
+            rc = lib().rhp_classify_batch(ctypes.byref(d), ctypes.byref(c), _stream(stream))
             if rc != 0:
                 raise RuntimeError(f"rhp_classify_batch failed: {rc}")
         return launch, fields, route
@@ -928,13 +949,10 @@ def parse_batch(buf: np.ndarray, off: np.ndarray, max_headers: int = 16, mode: i
                 **device_batch) -> Result:
     """Parse a host batch on the GPU (copies in, one launch, copies out).
     device_batch: DeviceBatch's fill / guard / bytes_shift (tests)."""
-    lib().rhp_set_impl(impl)
-    try:
+    with _impl(impl):
         db = DeviceBatch(buf, off, max_headers, mode, layout=layout, last_len=last_len, **device_batch)
         db.launch()
         return db.result()
-    finally:
-        lib().rhp_set_impl(IMPL_DFA)
 
 
 def classify_tables(names, routes=()):
@@ -976,14 +994,26 @@ def _classify_out(fields, route, n_names, n):
     return f, r
 
 
+def _batch_of(b_or_res) -> Batch:
+    """what a *_cpu form takes first: a Batch, or a Result that describes its batch"""
+    b = b_or_res.batch if isinstance(b_or_res, Result) else b_or_res
+    if b is None:
+        raise ValueError("this Result does not describe its batch")
+    return b
+
+
+def _session_arrays(sessions, results, starts=None, route=None):
+    """(sessions, results, req_start, route) of a *_cpu form, contiguous in their dtypes; None stays None"""
+    dtypes = (SESSION_DTYPE, SESSION_RESULT_DTYPE, np.uint64, np.uint16)
+    return tuple(a if a is None else np.ascontiguousarray(a, dtype=t) for a, t in zip((sessions, results, starts, route), dtypes))
+
+
 def classify_cpu(res_or_batch, names, routes=()):
     """rhp_cpu_classify_batch (include/rhp_host.h) over a parsed batch in host
     memory: a Result of emulate / parse_cpu_exact / parse_batch / DeviceBatch.result
     (its `batch`), or a Batch.  Returns (fields FIELDREF_DTYPE [n_names, n], route
     u16 [n]; RHP_ROUTE_NONE everywhere without routes)."""
-    b = res_or_batch.batch if isinstance(res_or_batch, Result) else res_or_batch
-    if b is None:
-        raise ValueError("this Result does not describe its batch")
+    b = _batch_of(res_or_batch)
     fields = np.zeros((len(names), b.n), dtype=FIELDREF_DTYPE)
     route = np.zeros(b.n, dtype=np.uint16)
     *_keep, c = _classify_desc(names, routes, _ptr(fields), _ptr(route))
@@ -1118,6 +1148,76 @@ def fixup_cpu(buf, off, sessions, max_headers: int = 16, emulate_dfa: bool = Fal
     return fixup_host(b, res, sessions, prefix)
 
 
+class _SessionRound:
+    """The device side of a session *_gpu form: `db` the speculative http DeviceBatch and `d` its descriptor, the
+    sessions uploaded as bytes (a device tensor is taken as it lies, with n_sessions; None: NULL, no session), and
+    results, req_start and, where asked for, route as Guarded buffers with the batch's guard, each stated as (bytes,
+    fill byte); fields, the same pair, is a plain tensor.  A form runs the steps (fixup and classify, or load), makes
+    its own call over the buffers, synchronises once, checks every guard (check; add: one more buffer for it) and
+    copies back (result)."""
+
+    def __init__(self, db: DeviceBatch, sessions, results, req_start, route=None, fields=None, n_sessions: int | None = None):
+        import torch
+        self.db, self.d, self.guard = db, db.desc(), db.guard
+        self.ns = n_sessions if n_sessions is not None else 0 if sessions is None else len(sessions)
+        if sessions is not None and not torch.is_tensor(sessions):
+            sessions = torch.from_numpy(np.ascontiguousarray(sessions).view(np.uint8).reshape(-1).copy()).to("cuda")
+        self.sessions = sessions
+        self.results, self.req_start, self.route = (
+            a if a is None else Guarded(name, a[0], db.guard, fill=a[1])
+            for name, a in (("results", results), ("req_start", req_start), ("route", route)))
+        self.fields = fields if fields is None else torch.full((fields[0],), fields[1], dtype=torch.uint8, device="cuda")
+        self.guarded = [g for g in (self.results, self.req_start, self.route) if g is not None]
+
+    def add(self, g: Guarded) -> Guarded:
+        """one more buffer for check()"""
+        self.guarded.append(g)
+        return g
+
+    def fixup(self) -> None:
+        """the parse launch, then rhp_fixup_sessions over what it left; nothing synchronised"""
+        self.db.launch()
+        fixup_sessions_device(self.d, self.sessions, self.ns, self.results.view, self.req_start.view)
+
+    def classify(self, names, routes) -> None:
+        """rhp_classify_sessions after fixup(), into fields and route"""
+        classify_sessions_device(self.d, self.sessions, self.ns, self.results.view, self.req_start.view, self.fields,
+                                 self.route.view, names, routes)
+
+    def load(self, records) -> None:
+        """(raw reqs, raw hdrs, raw http, session results, req_start, route) copied in, in place of fixup and classify"""
+        import torch
+        for t, a in zip((self.db.reqs, self.db.hdrs, self.db.http, self.results.view, self.req_start.view, self.route.view), records):
+            a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            if a.size:
+                t[: a.size].copy_(torch.from_numpy(a.copy()))
+
+    def check(self) -> None:
+        """every buffer's guard bytes, the batch's too (after the synchronise); nothing without guard"""
+        if self.guard:
+            self.db.check_guards()
+            for g in self.guarded:
+                g.check()
+
+    def result(self, route: bool = False):
+        """the host copies: (Result, session results [n_sessions], req_start as allocated), and route u16 [n] on request"""
+        out = (self.db.result(), self.results.view.cpu().numpy().view(SESSION_RESULT_DTYPE)[: self.ns],
+               self.req_start.view.cpu().numpy().view(np.uint64))
+        return out + (self.route.view.cpu().numpy().view(np.uint16)[: self.db.n],) if route else out
+
+
+def _fixup_round(buf, off, sessions, max_headers, impl, layout=LAYOUT_REQUEST_MAJOR, guard=0) -> _SessionRound:
+    """fixup_gpu's round, run and checked: gather_wide_gpu goes on over its device buffers"""
+    import torch
+    with _impl(impl):
+        db = DeviceBatch(buf, off, max_headers, MODE_HTTP, layout=layout, flags=BATCH_SPECULATIVE, guard=guard)
+        r = _SessionRound(db, sessions, (len(sessions) * SESSION_RESULT_DTYPE.itemsize, None), (max(db.n, 1) * 8, None))
+        r.fixup()
+        torch.cuda.synchronize()
+        r.check()
+    return r
+
+
 def fixup_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_DFA, layout: int = LAYOUT_REQUEST_MAJOR,
               with_batch: bool = False, guard: int = 0):
     """Speculative http batch on the GPU + rhp_fixup_sessions, one stream.
@@ -1125,29 +1225,8 @@ def fixup_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_DFA, l
     what the fix-up left: rhp_pack_dense can run over them).  guard (bytes,
     tests): the batch's buffers and the fix-up's two outputs are Guarded, and
     checked once both kernels have run."""
-    import torch
-    lib().rhp_set_impl(impl)
-    try:
-        db = DeviceBatch(buf, off, max_headers, MODE_HTTP, layout=layout, flags=BATCH_SPECULATIVE, guard=guard)
-        db.launch()
-        ds = torch.from_numpy(sessions.view(np.uint8).copy()).to("cuda")
-        gres = Guarded("results", len(sessions) * SESSION_RESULT_DTYPE.itemsize, guard)
-        gst = Guarded("req_start", max(db.n, 1) * 8, guard)
-        dres, dst = gres.view, gst.view
-        d = db.desc()
-        rc = lib().rhp_fixup_sessions(ctypes.byref(d), ctypes.c_void_p(ds.data_ptr()), len(sessions),
-                                      ctypes.c_void_p(dres.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
-                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
-        res = db.result()
-        if guard:
-            gres.check()
-            gst.check()
-        out = res, dres.cpu().numpy().view(SESSION_RESULT_DTYPE), dst.cpu().numpy().view(np.uint64)
-        return out + (db,) if with_batch else out
-    finally:
-        lib().rhp_set_impl(IMPL_DFA)
+    r = _fixup_round(buf, off, sessions, max_headers, impl, layout, guard)
+    return r.result() + ((r.db,) if with_batch else ())
 
 
 def fixup_sessions_device(d: Batch, sessions_t, n_sessions: int, results_t, starts_t, stream=None):
@@ -1155,11 +1234,9 @@ def fixup_sessions_device(d: Batch, sessions_t, n_sessions: int, results_t, star
     speculative batch's descriptor as rhp_parse_batch left it, sessions_t (8 * n_sessions bytes); the session
     results are left in results_t (16 * n_sessions bytes) and req_start in starts_t (8 * n bytes).  Nothing is
     synchronised or copied: the tensors are the call's only inputs and outputs."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     vp = ctypes.c_void_p
     rc = lib().rhp_fixup_sessions(ctypes.byref(d), vp(_addr(sessions_t)), n_sessions, vp(_addr(results_t)),
-                                  vp(_addr(starts_t)), vp(s.cuda_stream))
+                                  vp(_addr(starts_t)), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
 
@@ -1171,14 +1248,12 @@ def classify_sessions_device(d: Batch, sessions_t, n_sessions: int, results_t, s
     (2 * n bytes) are the outputs.  The host tables are classify_tables(names, routes), or `tables`: (text, names,
     routes) as that function returns them, where the caller owns the arrays (they may be freed or overwritten once
     the call has returned).  Nothing is synchronised or copied."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     text, nm, rt = tables if tables is not None else classify_tables(names, routes)
     c = Classify(_ptr(text), _ptr(nm) if len(nm) else None, _ptr(rt) if len(rt) else None, len(nm), len(rt),
                  _addr(fields_t) if len(nm) else None, _addr(route_t) if len(rt) else None)
     vp = ctypes.c_void_p
     rc = lib().rhp_classify_sessions(ctypes.byref(d), vp(_addr(sessions_t)), n_sessions, vp(_addr(results_t)),
-                                     vp(_addr(starts_t)), ctypes.byref(c), vp(s.cuda_stream))
+                                     vp(_addr(starts_t)), ctypes.byref(c), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_classify_sessions failed: {rc}")
 
@@ -1189,12 +1264,8 @@ def classify_sessions_cpu(b_or_res, sessions, results, starts, names, routes=())
     describes its batch (fixup_cpu's, fixup_gpu's), with the fix-up's session
     results and req_start.  Returns (fields FIELDREF_DTYPE [n_names, n], route
     u16 [n]) by record slot."""
-    b = b_or_res.batch if isinstance(b_or_res, Result) else b_or_res
-    if b is None:
-        raise ValueError("this Result does not describe its batch")
-    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
-    results = np.ascontiguousarray(results, dtype=SESSION_RESULT_DTYPE)
-    starts = np.ascontiguousarray(starts, dtype=np.uint64)
+    b = _batch_of(b_or_res)
+    sessions, results, starts, _ = _session_arrays(sessions, results, starts)
     fields = np.zeros((len(names), b.n), dtype=FIELDREF_DTYPE)
     route = np.zeros(b.n, dtype=np.uint16)
     *_keep, c = _classify_desc(names, routes, _ptr(fields), _ptr(route))
@@ -1214,33 +1285,17 @@ def classify_sessions_gpu(buf, off, sessions, names, routes=(), max_headers: int
     the session results hold it before the first launch, so that a slot the
     fix-up never wrote reads back as that byte."""
     import torch
-    lib().rhp_set_impl(impl)
-    try:
+    with _impl(impl):
         db = DeviceBatch(buf, off, max_headers, MODE_HTTP, layout=layout, flags=BATCH_SPECULATIVE, fill=fill)
-        ds = torch.from_numpy(np.ascontiguousarray(sessions).view(np.uint8).copy()).to("cuda")
-        dres = Guarded("results", len(sessions) * SESSION_RESULT_DTYPE.itemsize, fill=fill).view
-        dst = Guarded("req_start", max(db.n, 1) * 8, fill=fill).view
         # (the outputs hold 0xA5 first: the kernel writes every slot)
-        fields = torch.full((max(len(names) * db.n, 1) * FIELDREF_DTYPE.itemsize,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
-        route = torch.full((max(db.n, 1) * 2,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
-        *_keep, c = _classify_desc(names, routes, fields.data_ptr(), route.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        vp = ctypes.c_void_p
-        db.launch()
-        d = db.desc()
-        rc = lib().rhp_fixup_sessions(ctypes.byref(d), vp(ds.data_ptr()), len(sessions), vp(dres.data_ptr()),
-                                      vp(dst.data_ptr()), stream)
-        if rc != 0:
-            raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
-        rc = lib().rhp_classify_sessions(ctypes.byref(d), vp(ds.data_ptr()), len(sessions), vp(dres.data_ptr()),
-                                         vp(dst.data_ptr()), ctypes.byref(c), stream)
-        if rc != 0:
-            raise RuntimeError(f"rhp_classify_sessions failed: {rc}")
-        res = db.result()   # (synchronizes)
-        out = _classify_out(fields, route if len(routes) else None, len(names), db.n)
-        return out + (res, dres.cpu().numpy().view(SESSION_RESULT_DTYPE), dst.cpu().numpy().view(np.uint64))
-    finally:
-        lib().rhp_set_impl(IMPL_DFA)
+        r = _SessionRound(db, sessions, (len(sessions) * SESSION_RESULT_DTYPE.itemsize, fill), (max(db.n, 1) * 8, fill),
+                          route=(max(db.n, 1) * 2, GUARD_BYTE),
+                          fields=(max(len(names) * db.n, 1) * FIELDREF_DTYPE.itemsize, GUARD_BYTE))
+        r.fixup()
+        r.classify(names, routes)
+        torch.cuda.synchronize()
+        r.check()
+        return _classify_out(r.fields, r.route.view if len(routes) else None, len(names), db.n) + r.result()
 
 
 # ---------------------------------------------------------------------------
@@ -1406,10 +1461,8 @@ class DeviceResponses:
                          self.out_size, self.work.data_ptr())
 
     def launch(self, stream=None) -> None:
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
         d = self.desc()
-        rc = lib().rhp_write_responses(ctypes.byref(d), ctypes.c_void_p(s.cuda_stream))
+        rc = lib().rhp_write_responses(ctypes.byref(d), _stream(stream))
         if rc != 0:
             raise RuntimeError(f"rhp_write_responses failed: {rc}")
 
@@ -1471,12 +1524,8 @@ def reply_sessions_cpu(b_or_res, sessions, results, route, images, image_off, st
     Returns (replies SESSION_REPLY_DTYPE [n_sessions], total, out u8 [out_size]): every output held REPLY_POISON
     before the call.  out_size None: the exact size, from a sizes-only call first.  out_shift: `out` starts that
     many bytes after a 16-byte boundary."""
-    b = b_or_res.batch if isinstance(b_or_res, Result) else b_or_res
-    if b is None:
-        raise ValueError("this Result does not describe its batch")
-    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
-    results = np.ascontiguousarray(results, dtype=SESSION_RESULT_DTYPE)
-    route = np.ascontiguousarray(route, dtype=np.uint16)
+    b = _batch_of(b_or_res)
+    sessions, results, _, route = _session_arrays(sessions, results, route=route)
     image_off = np.ascontiguousarray(image_off, dtype=np.uint64)
     t = reply_table(images, image_off, static_mask)
     ns = len(sessions)
@@ -1485,9 +1534,7 @@ def reply_sessions_cpu(b_or_res, sessions, results, route, images, image_off, st
     def call(size, shift):
         replies = np.full(max(ns, 1) * SESSION_REPLY_DTYPE.itemsize, REPLY_POISON, dtype=np.uint8)
         total = np.full(8, REPLY_POISON, dtype=np.uint8)
-        raw = np.full(size + shift + 16, REPLY_POISON, dtype=np.uint8)
-        at = (-raw.ctypes.data) % 16 + shift
-        out = raw[at: at + size]
+        out = _aligned(size, shift, REPLY_POISON)
         o = ReplyOut(_ptr(replies), _ptr(total), _ptr(out) if size else None, size, _ptr(work))
         rc = host().rhp_cpu_reply_sessions(ctypes.byref(b), _ptr(sessions), ns, _ptr(results), _ptr(route),
                                            ctypes.byref(t), ctypes.byref(o))
@@ -1507,7 +1554,6 @@ def reply_sessions_device(d: Batch, sessions_t, n_sessions: int, results_t, rout
     sides, `out` out_shift bytes into its allocation) and hold REPLY_POISON first.  Returns finish(): synchronize,
     check the guards, (replies SESSION_REPLY_DTYPE [n_sessions], total, out u8 [out_size])."""
     import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     g = {"replies": Guarded("replies", max(n_sessions, 1) * SESSION_REPLY_DTYPE.itemsize, guard, fill=REPLY_POISON),
          "total": Guarded("total", 8, guard, fill=REPLY_POISON),
          "out": Guarded("out", max(out_size, 1), guard, fill=REPLY_POISON, shift=out_shift),
@@ -1517,7 +1563,7 @@ def reply_sessions_device(d: Batch, sessions_t, n_sessions: int, results_t, rout
                  out_size, g["work"].view.data_ptr())
     vp = ctypes.c_void_p
     rc = lib().rhp_reply_sessions(ctypes.byref(d), vp(_addr(sessions_t)), n_sessions, vp(_addr(results_t)),
-                                  vp(_addr(route_t)), ctypes.byref(t), ctypes.byref(o), vp(s.cuda_stream))
+                                  vp(_addr(route_t)), ctypes.byref(t), ctypes.byref(o), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_reply_sessions failed: {rc}")
 
@@ -1540,49 +1586,26 @@ def reply_sessions_gpu(buf, off, sessions, names, routes, resps_for_routes, stat
     route, the reply images) -> rhp_reply_sessions, on one stream with no synchronisation in between.  out_size
     None: every slot's worth of the largest image.  Returns (replies, total, out bytes) as reply_sessions_device;
     details: also (Result, session results, route u16 [n]) as the GPU left them."""
-    import torch
     arena, resps, fields = resps_for_routes
     if len(resps) != len(routes):
         raise ValueError("one response per route")
-    lib().rhp_set_impl(impl)
-    try:
+    with _impl(impl):
         db = DeviceBatch(buf, off, max_headers, MODE_HTTP, layout=layout, flags=BATCH_SPECULATIVE, guard=guard)
-        ns = len(sessions)
-        ds = torch.from_numpy(np.ascontiguousarray(sessions).view(np.uint8).copy()).to("cuda")
-        dres = Guarded("results", max(ns, 1) * SESSION_RESULT_DTYPE.itemsize, guard, fill=REPLY_POISON)
-        dst = Guarded("req_start", max(db.n, 1) * 8, guard, fill=REPLY_POISON)
-        droute = Guarded("route", max(db.n, 1) * 2, guard, fill=GUARD_BYTE)
-        *_keep, c = _classify_desc((), routes, None, droute.view.data_ptr())
+        r = _SessionRound(db, sessions, (max(len(sessions), 1) * SESSION_RESULT_DTYPE.itemsize, REPLY_POISON),
+                          (max(db.n, 1) * 8, REPLY_POISON), route=(max(db.n, 1) * 2, GUARD_BYTE))
         images = DeviceResponses(arena, resps, fields, date)
         if out_size is None:
             out_size = db.n * int(response_sizes(resps, fields).max())
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        vp = ctypes.c_void_p
-        db.launch()
-        d = db.desc()
-        rc = lib().rhp_fixup_sessions(ctypes.byref(d), vp(ds.data_ptr()), ns, vp(dres.view.data_ptr()),
-                                      vp(dst.view.data_ptr()), stream)
-        if rc != 0:
-            raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
-        rc = lib().rhp_classify_sessions(ctypes.byref(d), vp(ds.data_ptr()), ns, vp(dres.view.data_ptr()),
-                                         vp(dst.view.data_ptr()), ctypes.byref(c), stream)
-        if rc != 0:
-            raise RuntimeError(f"rhp_classify_sessions failed: {rc}")
+        r.fixup()
+        r.classify((), routes)
         images.launch()
-        finish = reply_sessions_device(d, ds, ns, dres.view, droute.view, images.out, images.out_off, static_mask,
-                                       out_size, guard, out_shift)
-        out = finish()
-        if guard:
-            db.check_guards()
-            for x in (dres, dst, droute):
-                x.check()
+        out = reply_sessions_device(r.d, r.sessions, r.ns, r.results.view, r.route.view, images.out, images.out_off,
+                                    static_mask, out_size, guard, out_shift)()   # (synchronizes)
+        r.check()
         if not details:
             return out
-        res = db.result()
-        return out + (res, dres.view.cpu().numpy().view(SESSION_RESULT_DTYPE)[:ns],
-                      droute.view.cpu().numpy().view(np.uint16)[: db.n])
-    finally:
-        lib().rhp_set_impl(IMPL_DFA)
+        res, results, _, route = r.result(route=True)
+        return out + (res, results, route)
 
 
 # ---------------------------------------------------------------------------
@@ -1612,22 +1635,14 @@ def gather_wide_cpu(b_or_res, sessions, results, starts, dreq, hc, caps=None, bo
     pack_dense_cpu).  caps (cap_slots, cap_hdrs, cap_body); None: the exact ones, from a totals-only call first.
     Returns (totals, slots [cap_slots], hdrs [cap_hdrs], body [cap_body]): every output held WIDE_POISON before
     the call.  body_shift: `body` starts that many bytes after a 16-byte boundary."""
-    b = b_or_res.batch if isinstance(b_or_res, Result) else b_or_res
-    if b is None:
-        raise ValueError("this Result does not describe its batch")
-    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
-    results = np.ascontiguousarray(results, dtype=SESSION_RESULT_DTYPE)
-    starts = np.ascontiguousarray(starts, dtype=np.uint64)
+    b = _batch_of(b_or_res)
+    sessions, results, starts, _ = _session_arrays(sessions, results, starts)
     dreq, hc = np.ascontiguousarray(dreq).view(np.uint8), np.ascontiguousarray(hc).view(np.uint8)
     work = np.full(wide_work_words(b.n) * 8, WIDE_POISON, dtype=np.uint8)
 
-    def aligned(size, shift=0):
-        raw = np.full(size + shift + 16, WIDE_POISON, dtype=np.uint8)
-        at = (-raw.ctypes.data) % 16 + shift
-        return raw[at: at + size]
-
     def call(caps):
-        totals, slots, hdrs, body = aligned(16), aligned(caps[0] * 64), aligned(caps[1] * 8), aligned(caps[2], body_shift)
+        totals, slots, hdrs, body = (_aligned(size, shift, WIDE_POISON) for size, shift in
+                                     ((16, 0), (caps[0] * 64, 0), (caps[1] * 8, 0), (caps[2], body_shift)))
         o = _wide_out(totals, slots, hdrs, body, work, caps)
         rc = host().rhp_cpu_gather_wide(ctypes.byref(b), _ptr(sessions), len(sessions), _ptr(results), _ptr(starts),
                                         _ptr(dreq), _ptr(hc), ctypes.byref(o))
@@ -1648,7 +1663,6 @@ def gather_wide_device(d: Batch, sessions_t, n_sessions: int, results_t, starts_
     bytes on both sides, `body` body_shift bytes into its allocation) and hold WIDE_POISON first.  Returns
     finish(): synchronize, check the guards, (totals, slots, hdrs, body) as gather_wide_cpu."""
     import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     caps = tuple(int(c) for c in caps)
     g = {"totals": Guarded("totals", 16, guard, fill=WIDE_POISON),
          "slots": Guarded("slots", max(caps[0] * 64, 1), guard, fill=WIDE_POISON),
@@ -1658,7 +1672,7 @@ def gather_wide_device(d: Batch, sessions_t, n_sessions: int, results_t, starts_
     o = _wide_out(*(g[k].view for k in ("totals", "slots", "hdrs", "body", "work")), caps)
     vp = ctypes.c_void_p
     rc = lib().rhp_gather_wide(ctypes.byref(d), vp(_addr(sessions_t)), n_sessions, vp(_addr(results_t)), vp(_addr(starts_t)),
-                               vp(_addr(dreq_t)), vp(_addr(hc_t)), ctypes.byref(o), vp(s.cuda_stream))
+                               vp(_addr(dreq_t)), vp(_addr(hc_t)), ctypes.byref(o), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_gather_wide failed: {rc}")
 
@@ -1676,14 +1690,12 @@ def pack_dense_device(db: "DeviceBatch", guard: int = 0, stream=None, outs=None)
     three outputs as Guarded device buffers (dreq 8n, hc 8n, lens16 2 * max_headers * n bytes), holding WIDE_POISON
     first.  outs: (dreq, hc, lens16) device tensors of those sizes that the caller made instead; nothing is then
     allocated or filled, and they are returned.  `db`: a DeviceBatch, or anything with its n, max_headers and desc()."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     n, m = db.n, db.max_headers
     if outs is None:
         outs = [Guarded(name, max(size, 8), guard, fill=WIDE_POISON) for name, size in
                 (("dreq", 8 * n), ("hc", 8 * n), ("lens16", 2 * m * n))]
     d = db.desc()
-    rc = lib().rhp_pack_dense(ctypes.byref(d), *(_addr(o.view if isinstance(o, Guarded) else o) for o in outs), s.cuda_stream)
+    rc = lib().rhp_pack_dense(ctypes.byref(d), *(_addr(o.view if isinstance(o, Guarded) else o) for o in outs), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_pack_dense failed: {rc}")
     return outs
@@ -1695,17 +1707,13 @@ def gather_wide_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_
     (fixup_gpu) -> rhp_pack_dense -> rhp_gather_wide.  caps None: the exact ones, from a totals-only call first.
     Returns (totals, slots, hdrs, body) as gather_wide_cpu; details: also (Result, session results, req_start,
     dreq u8 [8n], hc u8 [8n], lens16 u16 [max_headers * n]) as the GPU left them."""
-    import torch
-    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
-    res, results, starts, db = fixup_gpu(buf, off, sessions, max_headers, impl, with_batch=True, guard=guard)
-    n, ns = db.n, len(sessions)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda")
-    ds, dres, dst = dev(sessions), dev(results), dev(starts)
+    r = _fixup_round(buf, off, np.ascontiguousarray(sessions, dtype=SESSION_DTYPE), max_headers, impl, guard=guard)
+    db, n = r.db, r.db.n
     packed = pack_dense_device(db, guard)
-    d = db.desc()
 
     def call(caps):
-        return gather_wide_device(d, ds, ns, dres, dst, packed[0].view, packed[1].view, caps, guard, body_shift)()
+        return gather_wide_device(r.d, r.sessions, r.ns, r.results.view, r.req_start.view, packed[0].view, packed[1].view,
+                                  caps, guard, body_shift)()
 
     if caps is None:
         t = call((0, 0, 0))[0]
@@ -1718,7 +1726,7 @@ def gather_wide_gpu(buf, off, sessions, max_headers: int = 16, impl: int = IMPL_
     if not details:
         return out
     dreq, hc, lens = (x.view.cpu().numpy() for x in packed)
-    return out + (res, results, starts, dreq[: 8 * n], hc[: 8 * n], lens.view(np.uint16)[: max_headers * n])
+    return out + r.result() + (dreq[: 8 * n], hc[: 8 * n], lens.view(np.uint16)[: max_headers * n])
 
 
 def rebuild_records(n: int, max_headers: int, sessions, results, dreq, hc, lens16, totals, slots, hdrs, body):
@@ -1851,7 +1859,6 @@ def split_sessions_device(bytes_t, bytes_end: int, sess_off_t, n_sessions: int, 
     (n = cap) and rhp_fixup_sessions take, on the same stream, with no host step; finish(): synchronize, check
     the guards, (n_pieces, offsets, sessions) as split_sessions_cpu."""
     import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     cap = int(cap)
     outs = {"n_pieces": Guarded("n_pieces", 8, guard, fill=fill),
             "offsets": Guarded("offsets", 8 * (cap + 1), guard, fill=fill),
@@ -1861,7 +1868,7 @@ def split_sessions_device(bytes_t, bytes_end: int, sess_off_t, n_sessions: int, 
                  *(outs[k].view.data_ptr() for k in ("sessions", "work")))
     vp = ctypes.c_void_p
     rc = lib().rhp_split_sessions(vp(_addr(bytes_t)), bytes_end, vp(_addr(sess_off_t)), n_sessions, ctypes.byref(o),
-                                  vp(s.cuda_stream))
+                                  _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_split_sessions failed: {rc}")
 
@@ -1901,34 +1908,21 @@ def fixup_raw_gpu(session_bytes_list, cap: int, max_headers: int = 16, impl: int
     import torch
     buf, sess_off = pack_raw(session_bytes_list)
     end, ns, cap = int(sess_off[-1]), len(session_bytes_list), int(cap)
-    lib().rhp_set_impl(impl)
-    try:
+    with _impl(impl):
         db = DeviceBatch(buf, np.zeros(cap + 1, dtype=np.uint64), max_headers, MODE_HTTP, flags=BATCH_SPECULATIVE,
                          guard=guard)
         dso = torch.from_numpy(sess_off.view(np.int64)).to("cuda")
         outs, finish = split_sessions_device(db.bytes, end, dso, ns, cap, guard, fill=0)
         db.offsets = outs["offsets"].view.view(torch.int64)
-        db.launch()
-        gres = Guarded("results", ns * SESSION_RESULT_DTYPE.itemsize, guard)
-        gst = Guarded("req_start", max(cap, 1) * 8, guard)
-        d = db.desc()
-        rc = lib().rhp_fixup_sessions(ctypes.byref(d), ctypes.c_void_p(outs["sessions"].view.data_ptr()), ns,
-                                      ctypes.c_void_p(gres.view.data_ptr()), ctypes.c_void_p(gst.view.data_ptr()),
-                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
-        n_pieces, offsets, sessions = finish()
+        r = _SessionRound(db, outs["sessions"].view, (ns * SESSION_RESULT_DTYPE.itemsize, None), (max(cap, 1) * 8, None),
+                          n_sessions=ns)
+        r.fixup()
+        n_pieces, offsets, sessions = finish()   # (synchronizes)
         if n_pieces > cap:
             raise RuntimeError(f"fixup_raw_gpu: {n_pieces} pieces do not fit cap {cap}")
         db.host_off = offsets.copy()   # (result() describes the parsed batch over the split's offsets)
-        res = db.result()
-        if guard:
-            gres.check()
-            gst.check()
-        return (res, gres.view.cpu().numpy().view(SESSION_RESULT_DTYPE), gst.view.cpu().numpy().view(np.uint64),
-                n_pieces, offsets, sessions)
-    finally:
-        lib().rhp_set_impl(IMPL_DFA)
+        r.check()
+        return r.result() + (n_pieces, offsets, sessions)
 
 
 # The parser's other two entry points (rhp.h rhp_parse_messages): batches of
@@ -1988,11 +1982,9 @@ def parse_messages_device(bytes_t, bytes_size: int, off_t, n: int, kind: int, ma
     (16-byte aligned), off_t i64 / u64 [n + 1], last_len_t the same [n] or None; the records are left in msgs_t
     (u8, 16 * n bytes) and hdrs_t (u8, 8 * n * max_headers bytes; None when max_headers == 0).  Nothing is
     synchronised or copied: the tensors are the call's only inputs and outputs."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     b = MsgBatch(_addr(bytes_t), _addr(off_t), bytes_size, n, max_headers, kind, layout, _addr(msgs_t), _addr(hdrs_t),
                  _addr(last_len_t))
-    rc = lib().rhp_parse_messages(ctypes.byref(b), ctypes.c_void_p(s.cuda_stream))
+    rc = lib().rhp_parse_messages(ctypes.byref(b), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_parse_messages failed: {rc}")
 
@@ -2053,10 +2045,8 @@ def decode_chunked_device(bytes_t, bytes_size: int, off_t, n: int, decoders_t, r
     (16-byte aligned, decoded in place), off_t i64 / u64 [n + 1], decoders_t and results_t u8, 16 * n bytes each
     (16-byte aligned; the decoders are carried on in place).  Nothing is synchronised or copied: the tensors are
     the call's only inputs and outputs."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     b = ChunkedBatch(_addr(bytes_t), _addr(off_t), bytes_size, n, 0, _addr(decoders_t), _addr(results_t))
-    rc = lib().rhp_decode_chunked(ctypes.byref(b), ctypes.c_void_p(s.cuda_stream))
+    rc = lib().rhp_decode_chunked(ctypes.byref(b), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_decode_chunked failed: {rc}")
 
@@ -2130,13 +2120,11 @@ def frame_messages_device(bytes_t, bytes_size: int, off_t, n: int, kind: int, ma
     parse_messages_device left it; frames_t u8 (16 * n bytes, 16-byte aligned), fields_t u8 (4 * len(names) * n
     bytes), decoders_t u8 (16 * n bytes, 16-byte aligned) or None.  Nothing is synchronised or copied: the tensors
     are the call's only inputs and outputs (the names travel in the launch)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     text, nm, _ = classify_tables(names)
     b = MsgBatch(_addr(bytes_t), _addr(off_t), bytes_size, n, max_headers, kind, layout, _addr(msgs_t), _addr(hdrs_t), None)
     f = FrameArgs(_ptr(text), _ptr(nm) if len(nm) else None, len(nm), consume_trailer, _addr(fields_t) if len(nm) else None,
                   _addr(frames_t), _addr(decoders_t), 0)
-    rc = lib().rhp_frame_messages(ctypes.byref(b), ctypes.byref(f), ctypes.c_void_p(s.cuda_stream))
+    rc = lib().rhp_frame_messages(ctypes.byref(b), ctypes.byref(f), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_frame_messages failed: {rc}")
 
@@ -2345,11 +2333,9 @@ def walk_responses_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_se
     records are left in msgs_t (u8, 16 * n_slots_total bytes), hdrs_t (u8, 8 * n_slots_total * max_headers bytes;
     None when max_headers == 0), slots_t (u8, 32 * n_slots_total bytes) and results_t (u8, 16 * n_sessions bytes).
     Nothing is synchronised or copied: the tensors are the call's only inputs and outputs."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     w = _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
                     slots_t, results_t)
-    rc = lib().rhp_walk_responses(ctypes.byref(w), ctypes.c_void_p(s.cuda_stream))
+    rc = lib().rhp_walk_responses(ctypes.byref(w), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_walk_responses failed: {rc}")
 
@@ -2393,11 +2379,9 @@ def walk_resume_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sessi
     walk_responses_device, and states_t (u8, 32 * n_sessions bytes, 16-byte aligned), read at entry and written at
     exit.  It stays on the device: a chain of rounds hands the same tensor to every call.  Nothing is synchronised
     or copied."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     w = _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
                     slots_t, results_t)
-    rc = lib().rhp_walk_resume(ctypes.byref(w), _addr(states_t), ctypes.c_void_p(s.cuda_stream))
+    rc = lib().rhp_walk_resume(ctypes.byref(w), _addr(states_t), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_walk_resume failed: {rc}")
 
@@ -2464,12 +2448,10 @@ def walk_answers_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sess
     walk_resume_device (states_t None: the one-shot walk), req_off_t (i32 / u32 [n_sessions + 1]), head_bits_t (i32 /
     u32 words), answered_t (u8, 4 * n_sessions bytes) and slot_req_t (u8, 4 * n_slots_total bytes, or None), all
     4-byte aligned.  Nothing is synchronised or copied."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     w = _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
                     slots_t, results_t)
     x = WalkAsked(_addr(req_off_t), _addr(head_bits_t), n_req_total, 0, _addr(answered_t), _addr(slot_req_t))
-    rc = lib().rhp_walk_answers(ctypes.byref(w), _addr(states_t), ctypes.byref(x), ctypes.c_void_p(s.cuda_stream))
+    rc = lib().rhp_walk_answers(ctypes.byref(w), _addr(states_t), ctypes.byref(x), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_walk_answers failed: {rc}")
 
@@ -2526,13 +2508,11 @@ def lookup_walked_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_ses
     walk_responses_device or walk_resume_device left it; fields_t u8 (4 * len(names) * n_slots_total bytes).
     Nothing is synchronised or copied: the tensors are the call's only inputs and outputs (the names travel in
     the launch)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     text, nm, _ = classify_tables(names)
     w = _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
                     slots_t, results_t)
     l = WalkLookup(_ptr(text), _ptr(nm), len(nm), 0, _addr(fields_t))
-    rc = lib().rhp_lookup_walked(ctypes.byref(w), ctypes.byref(l), ctypes.c_void_p(s.cuda_stream))
+    rc = lib().rhp_lookup_walked(ctypes.byref(w), ctypes.byref(l), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_lookup_walked failed: {rc}")
 
@@ -2608,8 +2588,6 @@ def relay_walked_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sess
     (out_size bytes, any alignment; None with out_size 0) and work_t (8 * relay_work_words(n_slots_total) bytes).
     Nothing is synchronised or copied (the names and the date travel in the launch).  steps: the measuring call
     rhp_relay_walked_steps instead, which waits for the stream; returns (sizes, scan, copy) in microseconds."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     text, nm, _ = classify_tables(names)
     w = _walk_batch(bytes_t, bytes_size, sess_off_t, slot_off_t, n_sessions, n_slots_total, max_headers, flags, msgs_t, hdrs_t,
                     slots_t, results_t)
@@ -2617,9 +2595,9 @@ def relay_walked_device(bytes_t, bytes_size: int, sess_off_t, slot_off_t, n_sess
                   _addr(out_t), out_size, _addr(work_t))
     if steps:
         us = (ctypes.c_float * 3)()
-        rc = lib().rhp_relay_walked_steps(ctypes.byref(w), ctypes.byref(r), ctypes.c_void_p(s.cuda_stream), ctypes.byref(us))
+        rc = lib().rhp_relay_walked_steps(ctypes.byref(w), ctypes.byref(r), _stream(stream), ctypes.byref(us))
     else:
-        rc = lib().rhp_relay_walked(ctypes.byref(w), ctypes.byref(r), ctypes.c_void_p(s.cuda_stream))
+        rc = lib().rhp_relay_walked(ctypes.byref(w), ctypes.byref(r), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_relay_walked failed: {rc}")
     return tuple(us) if steps else None
@@ -2692,6 +2670,11 @@ def _forward_result(out_off, why, out, fwd_off, head_bits, n, n_sessions, fill=F
     return off, why[: 4 * n].view(np.uint32), out[:total] if total <= out.size else None, fo, head_bits[: 4 * words].view(np.uint32)
 
 
+def _forward_sizes(n, n_sessions):
+    """the bytes of (out_off, why, fwd_off, head_bits) as the host and the Guarded buffers are allocated"""
+    return 8 * (n + 1), max(4 * n, 4), 4 * (n_sessions + 1), max(4 * ((n + 31) // 32), 4)
+
+
 def forward_sessions_cpu(b_or_res, sessions, results, starts, route, n_routes: int, forward_mask: int, names=(),
                          extra: bytes = b"", out_size: int | None = None):
     """rhp_cpu_forward_sessions (include/rhp_host.h) over a speculative batch in host memory after a fix-up and a
@@ -2699,22 +2682,13 @@ def forward_sessions_cpu(b_or_res, sessions, results, starts, route, n_routes: i
     out_size None: the call runs twice, for the sizes and then with an `out` of exactly their sum.  Returns
     (out_off, why, out, fwd_off, head_bits) as _forward_result; all five held FORWARD_POISON before the call,
     head_bits at (n + 31) / 32 words."""
-    b = b_or_res.batch if isinstance(b_or_res, Result) else b_or_res
-    if b is None:
-        raise ValueError("this Result does not describe its batch")
-    sessions = np.ascontiguousarray(sessions, dtype=SESSION_DTYPE)
-    results = np.ascontiguousarray(results, dtype=SESSION_RESULT_DTYPE)
-    starts = np.ascontiguousarray(starts, dtype=np.uint64)
-    route = np.ascontiguousarray(route, dtype=np.uint16)
+    b = _batch_of(b_or_res)
+    sessions, results, starts, route = _session_arrays(sessions, results, starts, route)
     n, ns = b.n, len(sessions)
     work = np.zeros(forward_work_words(n, ns), dtype=np.uint64)
 
     def run(size):
-        off = np.full(8 * (n + 1), FORWARD_POISON, dtype=np.uint8)
-        why = np.full(max(4 * n, 4), FORWARD_POISON, dtype=np.uint8)
-        out = np.full(size, FORWARD_POISON, dtype=np.uint8)
-        fo = np.full(4 * (ns + 1), FORWARD_POISON, dtype=np.uint8)
-        hb = np.full(max(4 * ((n + 31) // 32), 4), FORWARD_POISON, dtype=np.uint8)
+        off, why, fo, hb, out = (np.full(k, FORWARD_POISON, dtype=np.uint8) for k in _forward_sizes(n, ns) + (size,))
         *_keep, f = _forward_desc(n_routes, forward_mask, names, extra, _ptr(off), _ptr(why), _ptr(out) if size else None, size,
                                   _ptr(fo), _ptr(hb), _ptr(work))
         rc = host().rhp_cpu_forward_sessions(ctypes.byref(b), _ptr(sessions) if ns else None, ns, _ptr(results) if ns else None,
@@ -2738,13 +2712,11 @@ def forward_sessions_device(d: Batch, sessions_t, n_sessions: int, results_t, st
     why_t (4 * n bytes), out_t (out_size bytes, any alignment; None with out_size 0), fwd_off_t (4 * (n_sessions + 1)
     bytes), head_bits_t (4 * ((n + 31) / 32) bytes) and work_t (8 * forward_work_words(n, n_sessions) bytes).
     Nothing is synchronised or copied (the names and the extra lines travel in the launches)."""
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
     *_keep, f = _forward_desc(n_routes, forward_mask, names, extra, _addr(out_off_t), _addr(why_t), _addr(out_t), out_size,
                               _addr(fwd_off_t), _addr(head_bits_t), _addr(work_t))
     vp = ctypes.c_void_p
     rc = lib().rhp_forward_sessions(ctypes.byref(d), vp(_addr(sessions_t)), n_sessions, vp(_addr(results_t)),
-                                    vp(_addr(starts_t)), vp(_addr(route_t)), ctypes.byref(f), vp(s.cuda_stream))
+                                    vp(_addr(starts_t)), vp(_addr(route_t)), ctypes.byref(f), _stream(stream))
     if rc != 0:
         raise RuntimeError(f"rhp_forward_sessions failed: {rc}")
 
@@ -2761,42 +2733,24 @@ def forward_sessions_gpu(buf, off, sessions, routes, forward_mask: int, names=()
     out as it was.  Returns (out_off, why, out, fwd_off, head_bits) as forward_sessions_cpu; details: also (Result,
     session results, req_start, route u16 [n]) as the GPU left them."""
     import torch
-    lib().rhp_set_impl(impl)
-    try:
+    with _impl(impl):
         db = DeviceBatch(buf, off, max_headers, MODE_HTTP, layout=layout, flags=BATCH_SPECULATIVE, guard=guard, fill=fill)
         n, ns = db.n, len(sessions)
-        ds = torch.from_numpy(np.ascontiguousarray(sessions, dtype=SESSION_DTYPE).view(np.uint8).copy()).to("cuda") if ns else None
-        dres = Guarded("results", max(ns, 1) * SESSION_RESULT_DTYPE.itemsize, guard, fill=fill)
-        dst = Guarded("req_start", max(n, 1) * 8, guard, fill=fill)
-        droute = Guarded("route", max(n, 1) * 2, guard, fill=GUARD_BYTE)
-        go = Guarded("out_off", 8 * (n + 1), guard, fill=fill)
-        gy = Guarded("why", max(4 * n, 4), guard, fill=fill)
-        gf = Guarded("fwd_off", 4 * (ns + 1), guard, fill=fill)
-        gb = Guarded("head_bits", max(4 * ((n + 31) // 32), 4), guard, fill=fill)
-        gw = Guarded("work", 8 * forward_work_words(n, ns), guard, fill=fill)
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        vp = ctypes.c_void_p
-        d = db.desc()
+        r = _SessionRound(db, np.ascontiguousarray(sessions, dtype=SESSION_DTYPE) if ns else None,
+                          (max(ns, 1) * SESSION_RESULT_DTYPE.itemsize, fill), (max(n, 1) * 8, fill), route=(max(n, 1) * 2, GUARD_BYTE))
+        sizes = _forward_sizes(n, ns) + (8 * forward_work_words(n, ns),)
+        go, gy, gf, gb, gw = (r.add(Guarded(name, size, guard, fill=fill))
+                              for name, size in zip(("out_off", "why", "fwd_off", "head_bits", "work"), sizes))
         if records is not None:
-            for t, a in zip((db.reqs, db.hdrs, db.http, dres.view, dst.view, droute.view), records):
-                a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-                if a.size:
-                    t[: a.size].copy_(torch.from_numpy(a.copy()))
+            r.load(records)
         else:
-            *_keep, c = _classify_desc((), routes, None, droute.view.data_ptr())
-            db.launch()
-            rc = lib().rhp_fixup_sessions(ctypes.byref(d), vp(_addr(ds)), ns, vp(dres.view.data_ptr()), vp(dst.view.data_ptr()), stream)
-            if rc != 0:
-                raise RuntimeError(f"rhp_fixup_sessions failed: {rc}")
-            rc = lib().rhp_classify_sessions(ctypes.byref(d), vp(_addr(ds)), ns, vp(dres.view.data_ptr()), vp(dst.view.data_ptr()),
-                                             ctypes.byref(c), stream)
-            if rc != 0:
-                raise RuntimeError(f"rhp_classify_sessions failed: {rc}")
+            r.fixup()
+            r.classify((), routes)
 
         def run(n_out):
             g = Guarded("out", max(n_out, 1), max(guard, 16) if out_shift else guard, fill=fill, shift=out_shift)
-            forward_sessions_device(d, ds, ns, dres.view, dst.view, droute.view, len(routes), forward_mask, names, extra, go.view,
-                                    gy.view, g.view if n_out else None, n_out, gf.view, gb.view, gw.view)
+            forward_sessions_device(r.d, r.sessions, ns, r.results.view, r.req_start.view, r.route.view, len(routes), forward_mask,
+                                    names, extra, go.view, gy.view, g.view if n_out else None, n_out, gf.view, gb.view, gw.view)
             torch.cuda.synchronize()
             return g
 
@@ -2809,16 +2763,12 @@ def forward_sessions_gpu(buf, off, sessions, routes, forward_mask: int, names=()
         gout = run(out_size)
         if not empty and int(go.view.cpu().numpy().view(np.uint64)[n]) > out_size:
             assert bool((gout.view == (fill or 0)).all()), "the requests do not fit, and out was written"
-        if guard:
-            db.check_guards()
-            for g in (dres, dst, droute, go, gy, gf, gb, gw, gout):
-                g.check()
+        r.add(gout)
+        r.check()
         off_b = go.view.cpu().numpy()
         out = _forward_result(off_b[:8] if empty else off_b, gy.view.cpu().numpy(), gout.view.cpu().numpy()[: max(out_size, 0)],
                               gf.view.cpu().numpy(), gb.view.cpu().numpy(), 0 if empty else n, ns, fill)
         if not details:
             return out
-        return out + (db.result(), dres.view.cpu().numpy().view(SESSION_RESULT_DTYPE)[:ns],
-                      dst.view.cpu().numpy().view(np.uint64)[:n], droute.view.cpu().numpy().view(np.uint16)[:n])
-    finally:
-        lib().rhp_set_impl(IMPL_DFA)
+        res, results, starts, route = r.result(route=True)
+        return out + (res, results, starts[:n], route)

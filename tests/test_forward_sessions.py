@@ -427,3 +427,24 @@ def test_gpu_empty_calls():
 def test_gpu_queue_feeds_walk_answers():
     for name in ("heads", "mixed"):
         check_hand_over(name, fs.forward_gpu(name), rhp.walk_answers_gpu)
+
+
+@pytest.mark.gpu
+def test_gpu_details_are_the_round_as_the_gpu_left_it():
+    """details=True: behind the five outputs (Result, session results, req_start, route), against the host's round.
+    The smallest input with every kind of session: two pipelined complete requests, one incomplete request, no bytes"""
+    buf, off, sess, _ = rhp.pack_sessions([fs.post(3) + fs.GET, fs.PARTIAL, b""])
+    n = len(off) - 1
+    got = rhp.forward_sessions_gpu(buf, off, sess, fs.ROUTES, fs.FORWARD_MASK, fs.DROP, fs.VIA, 4, guard=64, details=True)
+    assert len(got) == 9
+    wres, wresults, wstarts, wroute = fs.host_round_of(buf, off, sess, 4)
+    same(got[:5], rhp.forward_sessions_cpu(wres, sess, wresults, wstarts, wroute, len(fs.ROUTES), fs.FORWARD_MASK, fs.DROP, fs.VIA), "details")
+    res, results, starts, route = got[5:]
+    assert results.tolist() == wresults.tolist() and results["n_slots"].tolist() == [2, 1, 0]
+    assert len(starts) == len(route) == n
+    ready = np.flatnonzero(wres.http["result"] == 1)   # (of a slot that is not ready only the http result means anything)
+    assert ready.tolist() == [0, 1] and (res.http["result"] == wres.http["result"]).all()
+    assert (starts[ready] == wstarts[ready]).all() and (route[ready] == wroute[ready]).all() and route[ready].tolist() == [0, 0]
+    assert (res.http[ready] == wres.http[ready]).all()
+    for f in ("ret", "method_len", "path_off", "path_len", "method_off", "minor_version", "num_headers"):
+        assert (res.reqs[f][ready] == wres.reqs[f][ready]).all(), f

@@ -398,3 +398,26 @@ def test_gpu_no_session_and_no_slot():
     got = rhp.gather_wide_device(d0, ds, 1, dres, dst, ddq, dhc, (4, 4, 4), GUARD)()
     assert not any(int(got[0][f]) for f in got[0].dtype.names)
     untouched(got, "no slot")
+
+
+@pytest.mark.gpu
+def test_gpu_whole_round_in_one_call():
+    """rhp.gather_wide_gpu with details, the round's buffers left on the device between the fix-up and the gather:
+    the four outputs against the twin over the records the call returns, the session results against the host's
+    fix-up.  The smallest input with every kind of session: two pipelined complete requests (the first one chunked,
+    so a slot is wide and a body gathered), one incomplete request, no bytes"""
+    chunked = b"POST /c HTTP/1.1\r\nHost: c\r\nTransfer-Encoding: chunked\r\n\r\n5\r\nhello\r\n0\r\n\r\n"
+    buf, off, sess, _ = rhp.pack_sessions([chunked + b"GET /a HTTP/1.1\r\nHost: a\r\n\r\n", b"GET /b HTTP/1.1\r\nHost:", b""])
+    n = len(off) - 1
+    got = rhp.gather_wide_gpu(buf, off, sess, 4, guard=64, details=True)
+    assert len(got) == 10
+    res, results, starts, dreq, hc, lens = got[4:]
+    assert len(dreq) == len(hc) == 8 * n and len(lens) == 4 * n and lens.dtype == np.uint16
+    want_results = rhp.fixup_cpu(buf, off, sess, 4)[1]
+    assert results.tolist() == want_results.tolist() and results["n_slots"].tolist() == [2, 1, 0]
+    cpu = rhp.gather_wide_cpu(res, sess, results, starts, dreq, hc)
+    assert got[0] == cpu[0] and (got[1] == cpu[1]).all() and (got[2] == cpu[2]).all() and (got[3] == cpu[3]).all()
+    assert int(got[0]["n_wide"]) >= 1 and bytes(got[3]) == b"hello"
+    check(got[:4], statement(res, off, sess, results, starts, dreq, hc, 4), "one call")
+    short = rhp.gather_wide_gpu(buf, off, sess, 4, guard=64)
+    assert len(short) == 4 and short[0] == got[0] and all((a == b).all() for a, b in zip(short[1:], got[1:4]))
